@@ -8,7 +8,7 @@ Gram / log-det reduction, host scalar algebra.  Workload (BASELINE.json configs[
 n = 8192 1-D points at dx = 0.5 ell, RBF(ell ~ 0.2), nugget 1e-10, 6 EFT orders, synthetic
 coefficients; X and the right-hand sides are resident in HBM before the timed region.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU; every rank evaluates its own K grid points (weak scaling, no data-path
@@ -16,9 +16,11 @@ collective) and the fp64 likelihood slices are all-gathered over RCCL inside the
 Rank 0 prints ONE JSON line.  `python bench.py --gpus N` on its own starts the N ranks itself (child processes of
 torch.distributed.run, before this process touches a GPU) and relays rank 0's line.
 
-The timed K-step region is run `--repeats` times back to back (each bracketed by barrier + synchronize as the
-contract asks); `value` / `ms_per_step` are those of the MEDIAN region, min and max are reported beside it.
-Beyond the contract's keys the line carries (N = 1 only, outside the timed regions): `parity` (the GPU value at
+A plain run sets up, warms up, times ONE region of K steps (bracketed by barrier + synchronize as the contract asks),
+writes the outputs of that region if `--dump-outputs DIR` is given (DIR/<name>.npy, float64) and prints the line.
+Everything else is behind `--full`: there the timed K-step region is run `--repeats` times back to back (default 10);
+`value` / `ms_per_step` are those of the MEDIAN region, min and max are reported beside it.
+Beyond the contract's keys a `--full` line carries (N = 1 only, outside the timed regions): `parity` (the GPU value at
 ell = 0.2 against the CPU baseline's value of the same evaluation AND against the reference's own committed value,
 tests/golden/large_lml.json -- the latter at every N; the run exits non-zero above 1e-10),
 `cpu_baseline`, `kernel_time_shares` (HIP-event time of every kernel class inside the timed region), the
@@ -183,6 +185,25 @@ def golden_lml(n, r):
     except Exception:
         pass
     return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs DIR`: every array a caller of the timed path receives as DIR/<name>.npy in float64.  Above 64 MB in all, each
+    array keeps a fixed, seeded sample of its leading axis (the same rows on every run of the same arguments) and DIR/<name>_rows.npy
+    lists them."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and len(a) > 1:
+            keep = max(1, int(len(a) * (DUMP_LIMIT_BYTES // 2) / total))
+            rows = np.sort(np.random.RandomState(0).choice(len(a), keep, replace=False))
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def gradient_leg(ctx, X, Z, n):
@@ -430,10 +451,13 @@ def inproc_main(args):
     ells = np.linspace(0.19, 0.21, total) if total > 1 else np.array([0.2])
     descs = ctx0.desc_array([gsum_amd.describe_kernel(RBF(float(e)), 1) for e in ells])
 
+    last = {}
+
     def evaluate(batch, how):
         G, sld, info = grp.lml_resident(batch, 1e-10, gather=how)
         out = lml_from_gram_batch(G, sld, n, 0.0, 0.0, 1, 1) - jac
         out[np.asarray(info) != 0] = -np.inf
+        last.update(gram=G, sum_log_diag=sld, info=info)
         return out
 
     def sync_all():
@@ -455,24 +479,11 @@ def inproc_main(args):
         return el, vals, ctx0.kernel_profile()
 
     regions = [timed_region() for _ in range(max(1, args.repeats))]
-    prof_elapsed, _, prof = timed_region(1)
-    ctx0.set_option("profile_gemm", 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(last, lml=regions[-1][1]))
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, allvals, _ = regions[order[(len(order) - 1) // 2]]
     all_elapsed = [reg[0] for reg in regions]
-    gemm_ms, gemm_flops, gemm_launches = (prof["bulk_update"][k] for k in ("ms", "flops", "launches"))
-    launch_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    # every device's first grid point again, as a single evaluation on device 0 (another schedule, another GPU): bit-identical or rc 3
-    firsts = [int(gsum_amd.shard_range(total, rk, N)[0]) for rk in range(N)]
-    G1, s1, i1 = zip(*[ctx0.lml_resident([descs[i]], 1e-10) for i in firsts])
-    redo = lml_from_gram_batch(np.concatenate(G1), np.concatenate(s1), n, 0.0, 0.0, 1, 1) - jac
-    got_first = np.array([allvals[i] for i in firsts])
-    rank_check = {"what": "grid point 0 of every device's block: gathered value vs a single evaluation of the same descriptor on the "
-                          "first device", "ranks": N, "bit_identical": bool(np.array_equal(redo, got_first)),
-                  "max_rel": float(np.max(np.abs(redo - got_first) / np.abs(redo)))}
-    gpu_lml_02 = float(lml_from_gram_batch(*ctx0.lml_resident([gsum_amd.describe_kernel(RBF(0.2), 1)], 1e-10)[:2], n, 0.0, 0.0, 1, 1)[0] - jac)
-    ref_v = golden_lml(n, r)
-    ref_rel = None if ref_v is None else abs(gpu_lml_02 - ref_v) / abs(ref_v)
     groups, gsize = ctx0.get_option("wave_groups"), ctx0.get_option("wave_size")
     out = {"metric": "lml_evals_per_sec", "value": total / elapsed, "unit": "evals/s", "n_gpus": N, "steps": K, "warmup": W,
            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
@@ -488,20 +499,39 @@ def inproc_main(args):
            "repeats": {"n": len(all_elapsed), "stat": "median region (lower median)", "ms_per_step_median": elapsed / K * 1e3,
                        "ms_per_step_min": min(all_elapsed) / K * 1e3, "ms_per_step_max": max(all_elapsed) / K * 1e3,
                        "evals_per_s_all": [total / e for e in all_elapsed]},
-           "roofline": {"kernel": "k_gemm_ld3g on the first device of the group (every device runs the same launches)", "bound": "mfma",
-                        "achieved": launch_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": launch_tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None, "launches": gemm_launches,
-                        "avg_launch_us": gemm_ms * 1e3 / max(1, gemm_launches), "sum_launch_ms": gemm_ms, "region_ms": elapsed * 1e3,
-                        "busy_share_of_region": gemm_ms * 1e-3 / prof_elapsed},
-           "group": {"devices": ids, "rccl": grp.get("rccl"), "rccl_gathers": grp.get("rccl_gathers"),
-                     "devices_used": grp.get("devices_used"), "pipes_ok": [c_.get_option("pipes_ok") for c_ in grp.contexts]},
-           "rank_check": rank_check,
-           "parity": {"gpu": gpu_lml_02, "reference": ref_v, "rel": ref_rel, "bound": PARITY_BOUND,
-                      "status": "checked" if ref_rel is not None else "unchecked: no committed reference value for this size",
-                      "what": "TruncationGP.log_marginal_likelihood(log 0.2, ratio=0.5) on the first device vs the reference's committed "
-                              "value (tests/golden/large_lml.json)"},
            "gathered": {"length": int(len(allvals)), "expected": int(total), "finite": bool(np.isfinite(allvals).all())},
            "lml_sample": float(allvals[0])}
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return 0 if np.isfinite(allvals).all() else 3
+    prof_elapsed, _, prof = timed_region(1)
+    ctx0.set_option("profile_gemm", 0)
+    gemm_ms, gemm_flops, gemm_launches = (prof["bulk_update"][k] for k in ("ms", "flops", "launches"))
+    launch_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    # every device's first grid point again, as a single evaluation on device 0 (another schedule, another GPU): bit-identical or rc 3
+    firsts = [int(gsum_amd.shard_range(total, rk, N)[0]) for rk in range(N)]
+    G1, s1, i1 = zip(*[ctx0.lml_resident([descs[i]], 1e-10) for i in firsts])
+    redo = lml_from_gram_batch(np.concatenate(G1), np.concatenate(s1), n, 0.0, 0.0, 1, 1) - jac
+    got_first = np.array([allvals[i] for i in firsts])
+    rank_check = {"what": "grid point 0 of every device's block: gathered value vs a single evaluation of the same descriptor on the "
+                          "first device", "ranks": N, "bit_identical": bool(np.array_equal(redo, got_first)),
+                  "max_rel": float(np.max(np.abs(redo - got_first) / np.abs(redo)))}
+    gpu_lml_02 = float(lml_from_gram_batch(*ctx0.lml_resident([gsum_amd.describe_kernel(RBF(0.2), 1)], 1e-10)[:2], n, 0.0, 0.0, 1, 1)[0] - jac)
+    ref_v = golden_lml(n, r)
+    ref_rel = None if ref_v is None else abs(gpu_lml_02 - ref_v) / abs(ref_v)
+    out.update({
+        "roofline": {"kernel": "k_gemm_ld3g on the first device of the group (every device runs the same launches)", "bound": "mfma",
+                     "achieved": launch_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                     "frac": launch_tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None, "launches": gemm_launches,
+                     "avg_launch_us": gemm_ms * 1e3 / max(1, gemm_launches), "sum_launch_ms": gemm_ms, "region_ms": elapsed * 1e3,
+                     "busy_share_of_region": gemm_ms * 1e-3 / prof_elapsed},
+        "group": {"devices": ids, "rccl": grp.get("rccl"), "rccl_gathers": grp.get("rccl_gathers"),
+                  "devices_used": grp.get("devices_used"), "pipes_ok": [c_.get_option("pipes_ok") for c_ in grp.contexts]},
+        "rank_check": rank_check,
+        "parity": {"gpu": gpu_lml_02, "reference": ref_v, "rel": ref_rel, "bound": PARITY_BOUND,
+                   "status": "checked" if ref_rel is not None else "unchecked: no committed reference value for this size",
+                   "what": "TruncationGP.log_marginal_likelihood(log 0.2, ratio=0.5) on the first device vs the reference's committed "
+                           "value (tests/golden/large_lml.json)"}})
     print(json.dumps(out), flush=True)
     rc = 0
     if (ref_rel is not None and not ref_rel <= PARITY_BOUND) or not rank_check["bit_identical"] or not np.isfinite(allvals).all():
@@ -518,10 +548,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--n", "--points", dest="n", type=int, default=8192)
     ap.add_argument("--orders", type=int, default=6)
-    ap.add_argument("--cpu-evals", type=int, default=3, help="CPU-baseline evaluations (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=10,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated regions, per-kernel profile and roofline, parity against the reference and "
+                         "the CPU baseline, the other configurations (grids, predict, n = 2048, notebook, gradient)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed region computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-evals", type=int, default=3, help="--full: CPU-baseline evaluations (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed K-step region is run this many times back to back; value / ms_per_step are the "
-                         "median region, min and max are reported beside it")
+                         "median region, min and max are reported beside it (default: 1, with --full 10)")
     ap.add_argument("--groups", type=int, default=0, help="groups of the batch schedule (0 = library default, 3)")
     ap.add_argument("--group-size", type=int, default=0, help="evaluations per group at most (0 = library default, 8)")
     ap.add_argument("--inproc", type=int, default=0,
@@ -537,8 +572,10 @@ def main():
     ap.add_argument("--device", type=int, default=None, help="GPU index override (rehearsal: several ranks on one GPU)")
     ap.add_argument("--config", default="lml", choices=["lml", "predict"],
                     help="lml: the headline line; predict: only BASELINE config 5's predictive-variance leg (for profiling)")
-    ap.add_argument("--extras", type=int, default=1, help="0: skip the legs outside the contract (grids, predict)")
+    ap.add_argument("--extras", type=int, default=1, help="--full, 0: skip the legs outside the contract (grids, predict)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 10 if args.full else 1
 
     if args.inproc > 0:
         raise SystemExit(inproc_main(args))
@@ -588,12 +625,15 @@ def main():
     mine = ells[rank * K:(rank + 1) * K]
     descs = [gsum_amd.describe_kernel(RBF(float(e)), 1) for e in mine]
 
+    last = {}
+
     def evaluate(batch):
         """K build + Cholesky + fused solve for every descriptor (one call of the batch entry point: the library advances them in
         groups, one launch per kernel class and outer step), then the O(k^2) host algebra per evaluation."""
         G, sld, info = ctx.lml_resident(batch, 1e-10)
         out = lml_from_gram_batch(G, sld, n, 0.0, 0.0, 1, 1) - jac          # the O(k^2) algebra of all evaluations in one numpy pass
         out[np.asarray(info) != 0] = -np.inf
+        last.update(gram=G, sum_log_diag=sld, info=info)
         return out
 
     if args.groups > 0:
@@ -601,9 +641,16 @@ def main():
     if args.group_size > 0:
         ctx.set_option("wave_size", args.group_size)
     # set-up, not a step: the groups' workspaces (0.55 GB per evaluation in flight) are allocated on first use; do that here so
-    # that a small --warmup does not leave hipMalloc calls inside the timed region
-    evaluate([descs[i % len(descs)] for i in range(max(3, K))])
+    # that a small --warmup does not leave hipMalloc calls inside the timed region.  A call of 4 x groups x size evaluations or more
+    # (the library's threshold for a second cohort per group) allocates every workspace a longer call uses, so the set-up call is no
+    # longer than that.  It is repeated for one second: the first of ten back-to-back regions ran ~0.4 % below their median while the
+    # clocks settled, and a plain run times one region.
     groups, gsize = ctx.get_option("wave_groups"), ctx.get_option("wave_size")
+    setup = [descs[i % len(descs)] for i in range(max(3, min(K, 4 * groups * gsize)))]
+    t_setup = time.perf_counter()
+    evaluate(setup)
+    while time.perf_counter() - t_setup < 1.0:
+        evaluate(setup)
     in_flight = min(K, groups * gsize)
     gsize = min(gsize, -(-K // groups))            # a call shorter than groups x size fills the groups equally
     if W > 0:
@@ -630,15 +677,48 @@ def main():
         prof = ctx.kernel_profile()
         return el, allv, prof
 
-    # `repeats` plain timed regions (value = their median), then ONE more region with HIP events around every launch (a batch
-    # is ~170 launches since round 4: bracketing them all costs ~1 %): per-kernel times inside a timed region, each on the
+    # `repeats` plain timed regions (value = their median), then, with --full, ONE more region with HIP events around every launch
+    # (a batch is ~170 launches since round 4: bracketing them all costs ~1 %): per-kernel times inside a timed region, each on the
     # stream it is launched on.  The profiled region is reported, not counted.
     regions = [timed_region() for _ in range(max(1, args.repeats))]
-    prof_elapsed, _, prof = timed_region(1)
-    ctx.set_option("profile_gemm", 0)
+    if rank == 0 and args.dump_outputs:          # what the last timed region computed (N > 1: lml is the gathered grid)
+        dump_outputs(args.dump_outputs, dict(last, lml=regions[-1][1]))
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     elapsed, allvals, _ = regions[order[(len(order) - 1) // 2]]        # the median region (lower median)
     all_elapsed = [reg[0] for reg in regions]
+    head = {
+        "metric": "lml_evals_per_sec", "value": total / elapsed, "unit": "evals/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"full-recompute lml eval: n={n} 1-D RBF(ell~0.2) dx=0.5ell, nugget 1e-10, {r} orders"
+                               + (" (BASELINE configs[2], S3)" if (n, r) == (8192, 6) else
+                                  " (BASELINE configs[1], S2)" if (n, r) == (2048, 4) else " (not a BASELINE size: rehearsal)"),
+                   "n": n, "orders": r,
+                   "evals_per_gpu": K, "mode": "full-recompute", "evals_in_flight_per_gpu": in_flight,
+                   "batch_schedule": ("fewer than three evaluations per call: one after the other on the single-factorisation schedule "
+                                      "(persistent chain); " if K < 3 else
+                                      f"{groups} groups x up to {gsize} evaluations, one launch per kernel class and outer step; ")
+                                     + f"{ctx.get_option('wave_streams')} streams; GPU_MAX_HW_QUEUES "
+                                     + ("unset" if "GPU_MAX_HW_QUEUES" not in os.environ else os.environ["GPU_MAX_HW_QUEUES"])},
+        "repeats": {"n": len(all_elapsed), "stat": "median region (lower median)",
+                    "ms_per_step_median": elapsed / K * 1e3, "ms_per_step_min": min(all_elapsed) / K * 1e3,
+                    "ms_per_step_max": max(all_elapsed) / K * 1e3,
+                    "evals_per_s_all": [total / e for e in all_elapsed]},
+    }
+    if not args.full:                            # the plain run: the headline and nothing that takes runs of its own
+        finite = bool(np.isfinite(allvals).all())
+        if rank == 0:
+            print(json.dumps(dict(head, lml_sample=float(allvals[0]),
+                                  gathered={"length": int(len(allvals)), "expected": int(total), "finite": finite})), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        if len(allvals) != total or not finite:
+            raise SystemExit(3)
+        return
+    prof_elapsed, _, prof = timed_region(1)
+    ctx.set_option("profile_gemm", 0)
     gemm_ms, gemm_flops, gemm_launches = (prof["bulk_update"][k] for k in ("ms", "flops", "launches"))
 
     # every rank's first grid point, recomputed on rank 0 as a single evaluation (a different schedule: one factorisation alone):
@@ -776,24 +856,7 @@ def main():
                          "share_of_region_time": v["ms"] * 1e-3 / prof_elapsed}
                   for name, v in prof.items()}
         out = {
-            "metric": "lml_evals_per_sec", "value": total / elapsed, "unit": "evals/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"full-recompute lml eval: n={n} 1-D RBF(ell~0.2) dx=0.5ell, nugget 1e-10, {r} orders"
-                                   + (" (BASELINE configs[2], S3)" if (n, r) == (8192, 6) else
-                                      " (BASELINE configs[1], S2)" if (n, r) == (2048, 4) else " (not a BASELINE size: rehearsal)"),
-                       "n": n, "orders": r,
-                       "evals_per_gpu": K, "mode": "full-recompute", "evals_in_flight_per_gpu": in_flight,
-                       "batch_schedule": ("fewer than three evaluations per call: one after the other on the single-factorisation schedule "
-                                          "(persistent chain); " if K < 3 else
-                                          f"{groups} groups x up to {gsize} evaluations, one launch per kernel class and outer step; ")
-                                         + f"{ctx.get_option('wave_streams')} streams; GPU_MAX_HW_QUEUES "
-                                         + ("unset" if "GPU_MAX_HW_QUEUES" not in os.environ else os.environ["GPU_MAX_HW_QUEUES"])},
-            "repeats": {"n": len(all_elapsed), "stat": "median region (lower median)",
-                        "ms_per_step_median": elapsed / K * 1e3, "ms_per_step_min": min(all_elapsed) / K * 1e3,
-                        "ms_per_step_max": max(all_elapsed) / K * 1e3,
-                        "evals_per_s_all": [total / e for e in all_elapsed]},
+            **head,
             "single_eval_stage_ms": {"kernel_build": stage[0], "cholesky_fused_solve": stage[1],
                                      "finalize_d2h": stage[2], "gpu_total": stage[3]},
             "single_eval_schedule": single_schedule,

@@ -160,7 +160,7 @@ def test_streams_of_a_context_run_side_by_side(ctx):
     assert ctx.get_option("pipes_ok") == 1, ctx.get_option("pipe_overlap_permille")
     assert ctx.get_option("pipe_overlap_permille") >= 500
     lab = gsum_amd.lab_context(0)
-    assert lab.get_option("pipes_ok") == 1
+    assert lab.get_option("pipes_ok") == 1, (lab.get_option("pipe_overlap_permille"), lab.get_option("pipe_heals"))
     more = [_lib.HipContext(0) for _ in range(3)]
     try:
         assert [c.get_option("pipes_ok") for c in more] == [1, 1, 1]
