@@ -19,7 +19,7 @@ import collections
 import numpy as np
 from scipy.linalg import cho_solve as _cho_solve
 from scipy.linalg import solve_triangular
-from scipy.linalg.lapack import dpotrf
+from scipy.linalg.lapack import dpotrf, dpstrf
 from sklearn.gaussian_process.kernels import RBF, ConstantKernel, DotProduct, ExpSineSquared, Matern, RationalQuadratic
 
 from ._lib import FAMILY, GSUM_MAX_RHS, OP_ADD, OP_CONST, OP_LEAF, OP_POW, OP_WHITE, GradParam, KernelDesc
@@ -113,6 +113,8 @@ class CpuMatrix:
         self.A = np.array(A, dtype=float)
         self.n = self.A.shape[0]
         self.factored = False
+        self.pivoted = False
+        self.piv = None
 
     def to_host(self):
         return np.tril(self.A) if self.factored else self.A.copy()
@@ -194,6 +196,34 @@ class CpuContext:
             M.A = c
             M.factored = True
         return int(info)
+
+    def pstrf(self, M: CpuMatrix):
+        """gsum_sqrt_errors' pivoted factorisation: LAPACK dpstrf (lower, tol -1) -> (info, piv); info 0 or rank + 1, piv 0-based."""
+        self.calls["pstrf"] += 1
+        if M.factored:
+            raise ValueError("matrix is already factorised")
+        c, piv, rank, info = dpstrf(M.A, tol=-1.0, lower=1)
+        piv = np.asarray(piv, dtype=np.int64) - 1
+        if info != 0:
+            return int(rank) + 1, piv
+        M.A, M.factored, M.pivoted, M.piv = np.tril(c), True, True, piv
+        return 0, piv
+
+    def sqrt_errors(self, L: CpuMatrix, Y, mean=None, pivot=False, errors=True, md2=False):
+        """gsum_sqrt_errors: E = L^-1 P^T (Y - mean 1^T), md2_j = sum_i E_ij^2 (an unfactored L is factorised first)."""
+        self.calls["sqrt_errors"] += 1
+        if not L.factored:
+            info = self.pstrf(L)[0] if pivot else self.potrf(L)
+            if info:
+                raise np.linalg.LinAlgError(f"{'pstrf' if pivot else 'potrf'}: matrix is not positive definite (info {info})")
+        elif bool(L.pivoted) != bool(pivot):
+            raise ValueError("sqrt_errors: the matrix holds a " + ("pivoted" if L.pivoted else "unpivoted") + " factor")
+        Y = np.asarray(Y, dtype=float)
+        R = Y if mean is None else (Y.T - np.asarray(mean, dtype=float)).T
+        if pivot:
+            R = R[L.piv]
+        E = solve_triangular(L.A, R, lower=True)
+        return (E if errors else None), (np.sum(E * E, axis=0) if md2 else None)
 
     def factorize(self, desc, X, diag_add=0.0, series=None):
         K = self.kernel_matrix_dev(desc, X, diag_add=diag_add)

@@ -188,6 +188,7 @@ PROTOTYPES = {
     "gsum_mat_scale_series": (C.c_int, [_p, _p, C.POINTER(SeriesScale), _dp, _dp]),
     "gsum_predict_terms_series": (C.c_int, [_p, _p, _kp, _dp, C.c_int64, C.c_int32, _dp, C.c_int64, _dp, C.c_int32,
                                             C.POINTER(SeriesScale), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gsum_sqrt_errors": (C.c_int, [_p, _p, C.c_int32, _ip, _ip, _dp, _dp, C.c_int64, C.c_int64, _dp, _dp]),
     "gsum_mat_to_host": (C.c_int, [_p, _p, _dp]),
     "gsum_mat_n": (C.c_int64, [_p]),
     "gsum_mat_free": (None, [_p, _p]),
@@ -305,6 +306,8 @@ class DeviceMatrix:
         self._h = handle
         self.n = int(ctx._lib.gsum_mat_n(handle))
         self.factored = False
+        self.pivoted = False
+        self.piv = None
 
     def to_host(self) -> np.ndarray:
         out = np.empty((self.n, self.n))
@@ -456,6 +459,43 @@ class HipContext:
             except BaseException:
                 K.free()
                 raise
+
+    def pstrf(self, A: DeviceMatrix):
+        """LAPACK dpstrf (lower, tol -1) in place: ``(info, piv)`` -- info 0, or rank + 1 where A is rank-deficient (A is then left
+        as it was); piv (0-based) with P^T A P = L L^T, and A holds L in pivot order (gsum_sqrt_errors with k = 0)."""
+        info = C.c_int64(0)
+        piv = np.empty(A.n, dtype=np.int64)
+        self._check(self._lib.gsum_sqrt_errors(self._h, A._h, 1, piv.ctypes.data_as(_ip), C.byref(info), None, None, A.n, 0, None, None))
+        A.factored, A.pivoted, A.piv = info.value == 0, True, piv
+        return int(info.value), piv
+
+    def sqrt_errors(self, L: DeviceMatrix, Y, mean=None, pivot: bool = False, errors: bool = True, md2: bool = False):
+        """E = L^-1 P^T (Y - mean 1^T) for any number of columns (P = I for a plain factor) and md2_j = sum_i E_ij^2: ``(E, md2)``
+        (None where not asked for).  An unfactored L is factorised first (``pivot``: dpstrf, else potrf); numpy.linalg.LinAlgError
+        where that fails.  Y: (n,) or (n, k)."""
+        Y = _f64(Y)
+        squeeze = Y.ndim == 1
+        if squeeze:
+            Y = Y[:, None]
+        n, k = Y.shape
+        if n != L.n:
+            raise ValueError(f"Y has {n} rows, the factor {L.n}")
+        mean = None if mean is None else _f64(mean, (n,))
+        E = np.empty((n, k)) if errors else None
+        m2 = np.empty(k) if md2 else None
+        info = C.c_int64(0)
+        piv = np.empty(n, dtype=np.int64) if pivot else None
+        self._check(self._lib.gsum_sqrt_errors(self._h, L._h, 1 if pivot else 0, piv.ctypes.data_as(_ip) if pivot else None, C.byref(info),
+                                               _ptr(Y), _ptr(mean), n, k, _ptr(E), _ptr(m2)))
+        if info.value:
+            raise np.linalg.LinAlgError(f"{'pstrf' if pivot else 'potrf'}: matrix is not positive definite (info {info.value})")
+        L.factored, L.pivoted = True, bool(pivot)
+        if pivot:
+            L.piv = piv
+        if squeeze:
+            E = None if E is None else E[:, 0]
+            m2 = None if m2 is None else m2[0]
+        return E, m2
 
     def forward_gram(self, L: DeviceMatrix, rhs):
         rhs = _f64(rhs)

@@ -17,6 +17,7 @@
 #include "host/potrf.hip.h"
 #include "host/api_context.hip.h"
 #include "host/api_operators.hip.h"
+#include "host/pstrf.hip.h"
 #include "host/api_fused.hip.h"
 #include "host/wave.hip.h"
 #include "host/api_lml.hip.h"

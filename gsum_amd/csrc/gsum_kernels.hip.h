@@ -11,6 +11,7 @@
 //   k_finalize     Gram / log-det read-out of the bordered factorisation
 //   k_rowsumsq, k_scale_series, k_tri_multiply, k_grad_contract, k_grad_reduce*   prediction, series scaling, sampling and
 //                  gradient contractions
+//   k_pstrf_panel  the pivot steps of one panel of the pivoted Cholesky (dpstrf): workgroups meet at a grid barrier per step
 //   probes         fp64 MFMA issue rate, HBM store rate, workgroup placement under a CU mask
 //
 // Data layout: the factorisation works on ONE augmented row-major fp64 matrix
@@ -32,4 +33,5 @@
 #include "kernels/tile.hip.h"
 #include "kernels/solve.hip.h"
 #include "kernels/grad.hip.h"
+#include "kernels/pstrf.hip.h"
 #include "kernels/probes.hip.h"

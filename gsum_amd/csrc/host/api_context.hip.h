@@ -157,6 +157,7 @@ void gsum_destroy(gsum_ctx* ctx) {
         if (I->Z) (void)hipFree(I->Z);
     }
     if (ctx->scratch) (void)hipFree(ctx->scratch);
+    if (ctx->pscratch) (void)hipFree(ctx->pscratch);
     if (ctx->panel_stats) (void)hipFree(ctx->panel_stats);
     if (ctx->hbatch) (void)hipHostFree(ctx->hbatch);
     if (ctx->gws) (void)hipFree(ctx->gws);
@@ -286,8 +287,9 @@ int gsum_set_option(gsum_ctx* ctx, const char* name, int64_t value) {
         GS_CHECK(hipDeviceSynchronize());
         if (ctx->scratch) GS_CHECK(hipFree(ctx->scratch));
         if (ctx->gws) GS_CHECK(hipFree(ctx->gws));
-        ctx->scratch = ctx->gws = nullptr;
-        ctx->scratch_cap = ctx->gws_cap = 0;
+        if (ctx->pscratch) GS_CHECK(hipFree(ctx->pscratch));
+        ctx->scratch = ctx->gws = ctx->pscratch = nullptr;
+        ctx->scratch_cap = ctx->gws_cap = ctx->pscratch_cap = 0;
         gs_wave_release(ctx, false);                           // the groups' workspaces (their streams stay)
         for (int i = 0; i < ctx->n_slots_ready; ++i) {         // and the per-slot workspace matrices of the fused path
             gs_mat_release(ctx->slots[i].ws);

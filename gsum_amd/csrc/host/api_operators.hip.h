@@ -144,10 +144,8 @@ int gsum_mat_from_host(gsum_ctx* ctx, const double* Ah, int64_t n, gsum_mat** ou
     return 0;
 }
 
-int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
-    if (!ctx || !A || !info) return -2;
-    GS_CHECK(hipSetDevice(ctx->device));
-    if (A->factored) GS_FAIL("matrix is already factorised");
+// the factorisation of gsum_potrf_lower and of gsum_sqrt_errors (pivot = 0, and pivot = 1 on P^T A P), with its info
+static int gs_potrf_info(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
     if (gs_potrf(ctx, A)) return -1;
     if (gs_finalize(ctx, A)) return -1;
     GS_CHECK(hipStreamSynchronize(ctx->cur->sm));
@@ -163,6 +161,14 @@ int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
     if (*info > A->n) *info = A->n;     // cannot happen (identity padding), kept as a guard
     A->factored = (*info == 0);
     return 0;
+}
+
+int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
+    if (!ctx || !A || !info) return -2;
+    GS_CHECK(hipSetDevice(ctx->device));
+    if (A->factored) GS_FAIL("matrix is already factorised");
+    A->pivoted = 0;
+    return gs_potrf_info(ctx, A, info);
 }
 
 // Forward substitution on the border rows against an existing factor (right-looking, block by block):
@@ -349,47 +355,17 @@ int gsum_predict_terms_series(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc
                             cov_out);
 }
 
-static int gs_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n,
-                            int32_t d, const double* Xs, int64_t m, const double* RHS, int32_t k,
-                            const gsum_series_scale* sc, const double* ref_x, const double* ratio_x,
-                            const double* ref_s, const double* ratio_s, double* colsumsq, double* VtW, double* cov_out) {
-    if (!ctx || !L || !X || !Xs || !colsumsq) return -2;
-    GS_CHECK(hipSetDevice(ctx->device));
-    if (gs_check_desc(ctx, desc, d)) return -2;
-    if (!L->factored) GS_FAIL("predict_terms needs a factorised matrix");
-    if (n != L->n || m <= 0) GS_FAIL("bad shapes");
-    if (k < 0 || k > GSUM_MAX_RHS || (k > 0 && (!RHS || !VtW))) GS_FAIL("bad RHS / k");
-    const int64_t np = L->np, ld = L->ld, ldb = np + GS_BORDER;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_xs = 0, o_bt = up((size_t)m * d * 8), o_vw = o_bt + up((size_t)m * ldb * 8),
-                 o_ss = o_vw + up((size_t)m * 16 * 8), o_cv = o_ss + up((size_t)m * 8),
-                 o_sc = o_cv + (cov_out ? up((size_t)m * m * 8) : 0),
-                 total = o_sc + (sc ? up((size_t)2 * (n + m) * 8) : 0);
-    if (gs_upload_X(ctx, &ctx->op, X, n, d)) return -1;
-    if (gs_reserve(ctx, &ctx->scratch, &ctx->scratch_cap, total)) return -1;
-    char* base = (char*)ctx->scratch;
-    double *dXs = (double*)(base + o_xs), *Bt = (double*)(base + o_bt), *dVW = (double*)(base + o_vw),
-           *dSS = (double*)(base + o_ss), *dCov = (double*)(base + o_cv);
-    GS_CHECK(hipMemcpyAsync(dXs, Xs, (size_t)m * d * 8, hipMemcpyHostToDevice, ctx->cur->sm));
-    if (gs_launch_build<true>(ctx, ctx->cur->sm, Bt, ldb, dXs, ctx->op.X, m, n, m, np, d, desc, 0.0, 0)) return -1;
-    if (sc) {
-        // rows of Bt are the new points, columns the conditioning points
-        double* v = (double*)(base + o_sc);
-        double *d_ref_s = v, *d_rat_s = v + m, *d_ref_x = v + 2 * m, *d_rat_x = v + 2 * m + n;
-        GS_CHECK(hipMemcpyAsync(d_ref_s, ref_s, (size_t)m * 8, hipMemcpyHostToDevice, ctx->cur->sm));
-        GS_CHECK(hipMemcpyAsync(d_rat_s, ratio_s, (size_t)m * 8, hipMemcpyHostToDevice, ctx->cur->sm));
-        GS_CHECK(hipMemcpyAsync(d_ref_x, ref_x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->cur->sm));
-        GS_CHECK(hipMemcpyAsync(d_rat_x, ratio_x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->cur->sm));
-        hipLaunchKernelGGL(k_scale_series, dim3((unsigned)((n + 255) / 256), (unsigned)m), dim3(256), 0, ctx->cur->sm, Bt, ldb, (int)m,
-                           (int)n, d_ref_s, d_rat_s, d_ref_x, d_rat_x, *sc);
-        GS_CHECK(hipGetLastError());
-    }
+// Bt (m rows x np, leading dimension ldb) <- Bt L^-T: the blocked forward sweep of a factor against m right-hand sides held as ROWS
+// (V^T = kernel(Xs, X) L^-T of gs_predict_terms; E^T = (P^T (Y - mean 1^T))^T L^-T of gsum_sqrt_errors), enqueued on the current slot's
+// main stream (and, for large m, its auxiliary stream, joined again at the end).
+static int gs_fwd_sweep(gsum_ctx* ctx, gsum_mat* L, double* Bt, int64_t ldb, int64_t m) {
     // LOOK-AHEAD SWEEP (round 5; m >= 1024 rows, large orders): pairs of block columns are steps, two steps a macro-step.  The context's chain
     // stream carries what the next step needs -- P(a) (both panels of pair a, k_panel256), N(a) (pair b's 256 columns, K = 256), P(b), then NB:
     // the next macro-step's 512 columns with both pairs at once (K = 512) --, the main stream ONE far launch per macro-step for everything right
     // of those (K = 512), which the chain stream only meets again a macro-step later: the 64 latency-bound panel launches of n = 16384 (17 % of
     // the one-stream sweep: the chip idles while 128 waves solve) run beside a far launch instead of between two.  Column block q receives the
     // far launches of all earlier macro-steps, then NB of the macro-step before its own, then N: ascending k per element, bit-identical.
+    const int64_t np = L->np, ld = L->ld;
     if (m >= 1024 && ctx->predict_lookahead && ctx->predict_lazy && ctx->predict_panel256 && np >= ctx->lazy_min_np && ctx->cur->sa && L->T >= 8) {
         const int T = L->T, S2 = (T + 1) / 2;
         hipStream_t sc = ctx->cur->sa, sf = ctx->cur->sm;
@@ -498,6 +474,45 @@ static int gs_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* 
         GS_CHECK(hipStreamWaitEvent(ctx->cur->sm, ctx->cur->evS, 0));
     }
     }
+    return 0;
+}
+
+static int gs_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n,
+                            int32_t d, const double* Xs, int64_t m, const double* RHS, int32_t k,
+                            const gsum_series_scale* sc, const double* ref_x, const double* ratio_x,
+                            const double* ref_s, const double* ratio_s, double* colsumsq, double* VtW, double* cov_out) {
+    if (!ctx || !L || !X || !Xs || !colsumsq) return -2;
+    GS_CHECK(hipSetDevice(ctx->device));
+    if (gs_check_desc(ctx, desc, d)) return -2;
+    if (!L->factored) GS_FAIL("predict_terms needs a factorised matrix");
+    if (n != L->n || m <= 0) GS_FAIL("bad shapes");
+    if (k < 0 || k > GSUM_MAX_RHS || (k > 0 && (!RHS || !VtW))) GS_FAIL("bad RHS / k");
+    const int64_t np = L->np, ld = L->ld, ldb = np + GS_BORDER;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_xs = 0, o_bt = up((size_t)m * d * 8), o_vw = o_bt + up((size_t)m * ldb * 8),
+                 o_ss = o_vw + up((size_t)m * 16 * 8), o_cv = o_ss + up((size_t)m * 8),
+                 o_sc = o_cv + (cov_out ? up((size_t)m * m * 8) : 0),
+                 total = o_sc + (sc ? up((size_t)2 * (n + m) * 8) : 0);
+    if (gs_upload_X(ctx, &ctx->op, X, n, d)) return -1;
+    if (gs_reserve(ctx, &ctx->scratch, &ctx->scratch_cap, total)) return -1;
+    char* base = (char*)ctx->scratch;
+    double *dXs = (double*)(base + o_xs), *Bt = (double*)(base + o_bt), *dVW = (double*)(base + o_vw),
+           *dSS = (double*)(base + o_ss), *dCov = (double*)(base + o_cv);
+    GS_CHECK(hipMemcpyAsync(dXs, Xs, (size_t)m * d * 8, hipMemcpyHostToDevice, ctx->cur->sm));
+    if (gs_launch_build<true>(ctx, ctx->cur->sm, Bt, ldb, dXs, ctx->op.X, m, n, m, np, d, desc, 0.0, 0)) return -1;
+    if (sc) {
+        // rows of Bt are the new points, columns the conditioning points
+        double* v = (double*)(base + o_sc);
+        double *d_ref_s = v, *d_rat_s = v + m, *d_ref_x = v + 2 * m, *d_rat_x = v + 2 * m + n;
+        GS_CHECK(hipMemcpyAsync(d_ref_s, ref_s, (size_t)m * 8, hipMemcpyHostToDevice, ctx->cur->sm));
+        GS_CHECK(hipMemcpyAsync(d_rat_s, ratio_s, (size_t)m * 8, hipMemcpyHostToDevice, ctx->cur->sm));
+        GS_CHECK(hipMemcpyAsync(d_ref_x, ref_x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->cur->sm));
+        GS_CHECK(hipMemcpyAsync(d_rat_x, ratio_x, (size_t)n * 8, hipMemcpyHostToDevice, ctx->cur->sm));
+        hipLaunchKernelGGL(k_scale_series, dim3((unsigned)((n + 255) / 256), (unsigned)m), dim3(256), 0, ctx->cur->sm, Bt, ldb, (int)m,
+                           (int)n, d_ref_s, d_rat_s, d_ref_x, d_rat_x, *sc);
+        GS_CHECK(hipGetLastError());
+    }
+    if (gs_fwd_sweep(ctx, L, Bt, ldb, m)) return -1;
     std::vector<double> vw;
     if (k > 0) {
         // row sums of squares and V^T W in ONE pass over V^T (k_rowsumsq_vw)

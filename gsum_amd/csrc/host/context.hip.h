@@ -32,6 +32,9 @@ struct gsum_mat {
     double* cdump = nullptr;               // 2 x GS_CH_GMAX x 16 x 256 doubles: operand images of the window's rows
     unsigned long long* cstamps = nullptr; // T / 2 x GS_CH_STAMPS realtime stamps (option "chain_stamps")
     bool factored = false;
+    int pivoted = 0;                       // the factor is of P^T A P (gsum_sqrt_errors, pivot = 1): A's rows / columns in pivot order
+    int* dperm = nullptr;                  // ... and P on the device (n entries: original index of row i), and on the host
+    std::vector<int64_t> perm;
 };
 
 // One evaluation pipeline: a main + a high-priority panel stream, the events that tie them together, a
@@ -194,6 +197,7 @@ struct gsum_ctx {
     gs_inputs* in = &res;
     const int32_t* set_of = nullptr;   // the current call's right-hand-side set per evaluation (host array; NULL: set 0 throughout)
     double* scratch = nullptr; size_t scratch_cap = 0;
+    double* pscratch = nullptr; size_t pscratch_cap = 0;    // pivoted Cholesky: two trailing-matrix buffers, the panel, its bookkeeping
     double* hbatch = nullptr; size_t hbatch_cap = 0;   // pinned host buffer for the fused paths' result blocks (258 doubles each)
     double* gws = nullptr; size_t gws_cap = 0;     // gradient path: U = L^-T, R^-1, V^T, per-parameter partials
     double timers[4] = {0, 0, 0, 0};

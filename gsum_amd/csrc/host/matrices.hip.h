@@ -67,6 +67,7 @@ static void gs_mat_release(gsum_mat* m) {
     if (m->cflags) (void)hipFree(m->cflags);
     if (m->cdump) (void)hipFree(m->cdump);
     if (m->cstamps) (void)hipFree(m->cstamps);
+    if (m->dperm) (void)hipFree(m->dperm);
     delete m;
 }
 

@@ -158,6 +158,11 @@ int gsum_predict_terms_series(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc
                               const double* Xs, int64_t m, const double* RHS, int32_t k, const gsum_series_scale* sc,
                               const double* ref_x, const double* ratio_x, const double* ref_s, const double* ratio_s,
                               double* colsumsq, double* VtW, double* cov_out);
+/* Diagnostic square roots (gsum diagnostics.py:58-61, 100-114; helpers.py:185-199): an unfactored A is factorised in place first -- pivot 0
+ * as gsum_potrf_lower, 1 as LAPACK dpstrf (lower, tol -1; piv: n 0-based); *info 0, or (rank | bad pivot) + 1.  Then, any k >= 0:
+ * E = L^-1 P^T (Y - mean 1^T) (n x k row-major; NULL: skip), md2[j] = sum_i E_ij^2 (NULL: skip).  Full contract: DESIGN.md section 11. */
+int gsum_sqrt_errors(gsum_ctx* ctx, gsum_mat* A, int32_t pivot, int64_t* piv, int64_t* info, const double* Y, const double* mean,
+                     int64_t n, int64_t k, double* E, double* md2);
 /* copy out: the full symmetric matrix (before potrf) or L with a zeroed upper triangle (after) */
 int gsum_mat_to_host(gsum_ctx* ctx, const gsum_mat* A, double* out);
 int64_t gsum_mat_n(const gsum_mat* A);
