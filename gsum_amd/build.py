@@ -6,6 +6,8 @@
 ``libgsum_hip_lab.so``  the same sources with -DGSUM_LAB: plus include/gsum_hip_debug.h (diagnostics, probes, microbenchmarks,
                         schedule switches); what tools/ and the schedule-equivalence tests load.  Built by ``--lab`` / ``build(lab=True)``
                         and by ``__graft_entry__.build()``.
+``libgsum_vario.so``    the variogram (include/gsum_vario.h): its own small library, built by every product ``build()`` with its own
+                        dependency list and up-to-date check.
 """
 from __future__ import annotations
 
@@ -24,6 +26,10 @@ HOST_PARTS = ("context", "gemm", "matrices", "potrf", "api_context", "api_operat
 DEPS += [os.path.join(HERE, "csrc", "host", f"{p}.hip.h") for p in HOST_PARTS]
 OUT = os.path.join(HERE, "libgsum_hip.so")
 OUT_LAB = os.path.join(HERE, "libgsum_hip_lab.so")
+VARIO_SRC = os.path.join(HERE, "csrc", "gsum_vario.hip")
+VARIO_MAP = os.path.join(HERE, "csrc", "gsum_vario.map")                 # linker version script: only gsum_vario_* exported
+VARIO_DEPS = [VARIO_SRC, VARIO_MAP, os.path.join(HERE, "csrc", "kernels", "variogram.hip.h"), os.path.join(ROOT, "include", "gsum_vario.h")]
+OUT_VARIO = os.path.join(HERE, "libgsum_vario.so")
 
 
 def hipcc_path():
@@ -33,12 +39,26 @@ def hipcc_path():
     raise RuntimeError("hipcc not found")
 
 
-def up_to_date(out=OUT):
-    return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in DEPS)
+def up_to_date(out=OUT, deps=None):
+    return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in (DEPS if deps is None else deps))
+
+
+def build_vario(force: bool = False, verbose: bool = False) -> str:
+    """libgsum_vario.so: the product's hipcc flags, only gsum_vario_* exported."""
+    if not force and up_to_date(OUT_VARIO, VARIO_DEPS):
+        return OUT_VARIO
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"), "-Wl,--version-script=" + VARIO_MAP, "-o", OUT_VARIO, VARIO_SRC]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return OUT_VARIO
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     out = OUT_LAB if lab else OUT
+    if not lab:
+        build_vario(force=force, verbose=verbose)
     if not force and up_to_date(out):
         return out
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",

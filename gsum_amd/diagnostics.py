@@ -6,8 +6,10 @@ resident until ``close()``.  Errors and Mahalanobis distances of any number of c
 What is O(n x curves) on the host in the reference stays on the host here (individual errors, chi2, credible intervals, the
 default samples), with the reference's own arithmetic.
 
-Not provided: ``GraphicalDiagnostic`` and its plotting, ``variogram`` / ``VariogramFourthRoot``, ``TruncationPointwise``, and a
-device eigensolver (``eigen_errors`` runs on ``backend='cpu'`` only).
+``Diagnostic.variogram`` is ``VariogramFourthRoot`` (variogram.py, libgsum_vario.so) followed by its ``compute()``.
+
+Not provided: ``GraphicalDiagnostic`` and its plotting, ``TruncationPointwise``, and a device eigensolver (``eigen_errors`` runs
+on ``backend='cpu'`` only).
 """
 from __future__ import annotations
 
@@ -178,6 +180,16 @@ class Diagnostic:
         k = np.asarray(self.cov).shape[-1]
         logs = 2 * np.sum(np.log(np.diag(self.cov))) - 2 * np.sum(np.log(np.diag(L0)))
         return 0.5 * (tr + dist - k + logs)
+
+    @staticmethod
+    def variogram(X, y, bin_bounds, device=None, backend=None):
+        R"""The variogram of the curves y (shape (N,) or (n_curves, N)) at inputs X: (v, bin_locations, gamma, lower, upper), v the
+        VariogramFourthRoot and the rest its ``compute(rt_scale=False)`` (diagnostics.py:173-194)."""
+        from .variogram import VariogramFourthRoot
+        v = VariogramFourthRoot(X, y, bin_bounds, device=device, backend=backend)
+        bin_locations = v.bin_locations
+        gamma, lower, upper = v.compute(rt_scale=False)
+        return v, bin_locations, gamma, lower, upper
 
     def credible_interval(self, y, intervals):
         """The credible interval diagnostic, shape ([n_curves], n_intervals) (diagnostics.py:148-171)."""
