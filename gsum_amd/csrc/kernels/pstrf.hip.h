@@ -31,7 +31,8 @@ __global__ __launch_bounds__(256) void k_pstrf_init(const double* A, int64_t ld,
     double m = -INFINITY;
     for (int i = threadIdx.x; i < n; i += 256) {
         const double v = A[(int64_t)i * ld + i];
-        m = (v > m || v != v) ? v : m;          // a NaN diagonal propagates (LAPACK: AJJ NaN -> rank 0)
+        m = (v > m || v != v) ? v : m;          // a NaN diagonal propagates into dstop: step 0 stops, info 1 (LAPACK stops too, at a rank
+                                                // that depends on where the NaN lies: rank 4 for 2 I_5 with A(3,3) NaN, 0 with A(1,1) NaN)
         perm[i] = i;
     }
 #pragma unroll
