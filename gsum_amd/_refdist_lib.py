@@ -1,0 +1,130 @@
+"""ctypes binding of libgsum_refdist.so (C ABI: include/gsum_refdist.h), the reference distributions' own library."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libgsum_refdist.so")
+
+_p = C.c_void_p
+_dp = C.POINTER(C.c_double)
+PROTOTYPES = {
+    "gsum_refdist_last_error": (C.c_char_p, []),
+    "gsum_refdist_create": (C.c_int, [C.c_int32, _dp, C.c_int64, C.c_int64, C.POINTER(_p)]),
+    "gsum_refdist_sort_columns": (C.c_int, [_p, _dp]),
+    "gsum_refdist_row_percentiles": (C.c_int, [_p, _dp, C.c_int32, _dp]),
+    "gsum_refdist_qq_bands": (C.c_int, [_p, _dp, C.c_int32, _dp, _dp]),
+    "gsum_refdist_coverage": (C.c_int, [_p, _dp, _dp, C.c_int32, C.POINTER(C.c_int64)]),
+    "gsum_refdist_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_refdist_free": (None, [_p]),
+}
+PHASES = ("h2d", "transpose", "column_sort", "percentiles", "coverage", "d2h")
+
+_lib = None
+
+
+def load_library(path: str | None = None):
+    """dlopen libgsum_refdist.so and attach the prototypes.  Raises if it is absent (``python -m gsum_amd.build`` builds it)."""
+    global _lib
+    if _lib is not None and path is None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise RuntimeError(f"{p} is missing: build it with `python -m gsum_amd.build`")
+    lib = C.CDLL(p)
+    for name, (res, args) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    if path is None:
+        _lib = lib
+    return lib
+
+
+def _d(a):
+    return a.ctypes.data_as(_dp) if a is not None else None
+
+
+def _check(lib, rc):
+    if rc:
+        raise ValueError(lib.gsum_refdist_last_error().decode())
+
+
+def _matrix(a, name):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"{name} must be 2-D, got shape {a.shape}")
+    return a
+
+
+class DeviceRefDist:
+    """One n x m matrix resident on the device (uploaded once) and the operations of include/gsum_refdist.h on it."""
+
+    def __init__(self, device, A):
+        self._h = None
+        self._lib = lib = load_library()
+        A = _matrix(A, "A")
+        self.n, self.m = A.shape
+        h = C.c_void_p()
+        _check(lib, lib.gsum_refdist_create(int(device), _d(A), self.n, self.m, C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the device matrix is freed")
+        return self._h
+
+    def sort_columns(self, return_sorted=True):
+        """The matrix becomes numpy.sort(matrix, axis=0) on the device; returned when ``return_sorted``."""
+        out = np.empty((self.n, self.m)) if return_sorted else None
+        _check(self._lib, self._lib.gsum_refdist_sort_columns(self._handle(), _d(out)))
+        return out
+
+    def row_percentiles(self, q):
+        q = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        out = np.empty((q.shape[0], self.n))
+        _check(self._lib, self._lib.gsum_refdist_row_percentiles(self._handle(), _d(q), q.shape[0], _d(out)))
+        return out
+
+    def qq_bands(self, q, return_sorted=False):
+        q = np.ascontiguousarray(q, dtype=np.float64).ravel()
+        bands = np.empty((q.shape[0], self.n))
+        srt = np.empty((self.n, self.m)) if return_sorted else None
+        _check(self._lib, self._lib.gsum_refdist_qq_bands(self._handle(), _d(q), q.shape[0], _d(bands), _d(srt)))
+        return bands, srt
+
+    def coverage(self, lower, upper):
+        """int64 counts (m, K) of the points of each column strictly inside each of the K intervals (lower, upper: K x n)."""
+        lower = _matrix(lower, "lower")
+        upper = _matrix(upper, "upper")
+        if lower.shape != upper.shape or lower.shape[1] != self.n:
+            raise ValueError(f"lower and upper must both be (K, {self.n}), got {lower.shape} and {upper.shape}")
+        K = lower.shape[0]
+        counts = np.zeros((self.m, K), dtype=np.int64)
+        _check(self._lib, self._lib.gsum_refdist_coverage(self._handle(), _d(lower), _d(upper), K, counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return counts
+
+    def times(self, reset=False):
+        """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
+        ms = np.zeros(len(PHASES))
+        _check(self._lib, self._lib.gsum_refdist_times(self._handle(), _d(ms), int(bool(reset))))
+        return dict(zip(PHASES, ms.tolist()))
+
+    def free(self):
+        if getattr(self, "_h", None) is not None:
+            self._lib.gsum_refdist_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

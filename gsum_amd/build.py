@@ -8,6 +8,8 @@
                         and by ``__graft_entry__.build()``.
 ``libgsum_vario.so``    the variogram (include/gsum_vario.h): its own small library, built by every product ``build()`` with its own
                         dependency list and up-to-date check.
+``libgsum_refdist.so``  the reference distributions of GraphicalDiagnostic (include/gsum_refdist.h): column sort, row percentiles,
+                        interval coverage.  Its own small library, built like the variogram's.
 """
 from __future__ import annotations
 
@@ -30,6 +32,10 @@ VARIO_SRC = os.path.join(HERE, "csrc", "gsum_vario.hip")
 VARIO_MAP = os.path.join(HERE, "csrc", "gsum_vario.map")                 # linker version script: only gsum_vario_* exported
 VARIO_DEPS = [VARIO_SRC, VARIO_MAP, os.path.join(HERE, "csrc", "kernels", "variogram.hip.h"), os.path.join(ROOT, "include", "gsum_vario.h")]
 OUT_VARIO = os.path.join(HERE, "libgsum_vario.so")
+REFDIST_SRC = os.path.join(HERE, "csrc", "gsum_refdist.hip")
+REFDIST_MAP = os.path.join(HERE, "csrc", "gsum_refdist.map")             # linker version script: only gsum_refdist_* exported
+REFDIST_DEPS = [REFDIST_SRC, REFDIST_MAP, os.path.join(HERE, "csrc", "kernels", "refdist.hip.h"), os.path.join(ROOT, "include", "gsum_refdist.h")]
+OUT_REFDIST = os.path.join(HERE, "libgsum_refdist.so")
 
 
 def hipcc_path():
@@ -55,10 +61,24 @@ def build_vario(force: bool = False, verbose: bool = False) -> str:
     return OUT_VARIO
 
 
+def build_refdist(force: bool = False, verbose: bool = False) -> str:
+    """libgsum_refdist.so: the product's hipcc flags, only gsum_refdist_* exported."""
+    if not force and up_to_date(OUT_REFDIST, REFDIST_DEPS):
+        return OUT_REFDIST
+    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"), "-Wl,--version-script=" + REFDIST_MAP, "-o", OUT_REFDIST,
+           REFDIST_SRC]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    return OUT_REFDIST
+
+
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     out = OUT_LAB if lab else OUT
     if not lab:
         build_vario(force=force, verbose=verbose)
+        build_refdist(force=force, verbose=verbose)
     if not force and up_to_date(out):
         return out
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
@@ -71,5 +91,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
+    print(OUT_VARIO)
+    print(OUT_REFDIST)
     if "--lab" in sys.argv:
         print(build(force="--force" in sys.argv, verbose=True, lab=True))

@@ -8,8 +8,11 @@ default samples), with the reference's own arithmetic.
 
 ``Diagnostic.variogram`` is ``VariogramFourthRoot`` (variogram.py, libgsum_vario.so) followed by its ``compute()``.
 
-Not provided: ``GraphicalDiagnostic`` and its plotting, ``TruncationPointwise``, and a device eigensolver (``eigen_errors`` runs
-on ``backend='cpu'`` only).
+``GraphicalDiagnostic`` (graphical.py) owns a ``Diagnostic`` and puts its results beside reference distributions made by simulation;
+the band stage of those runs in libgsum_refdist.so (refdist.py).
+
+Not provided: ``TruncationPointwise`` and a device eigensolver (``eigen_errors`` runs on ``backend='cpu'`` only, and with it the
+eigen panels of ``GraphicalDiagnostic``).
 """
 from __future__ import annotations
 
