@@ -13,6 +13,9 @@ import weakref
 
 import numpy as np
 
+from ._backend import resolve_device
+from ._sidelib import attach
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -249,12 +252,7 @@ def load_library(path: str | None = None, lab: bool = False):
             raise RuntimeError(
                 f"{p} not found: the HIP extension is not built. Run `python -m gsum_amd.build" + (" --lab" if lab else "") + "` "
                 "(hipcc --offload-arch=gfx950). The 'hip' backend has no CPU fallback.")
-        lib = C.CDLL(p)
-        protos = dict(PROTOTYPES, **LAB_PROTOTYPES) if lab else PROTOTYPES
-        for name, (res, args) in protos.items():
-            fn = getattr(lib, name)        # AttributeError if the symbol is missing
-            fn.restype = res
-            fn.argtypes = args
+        lib = attach(C.CDLL(p), dict(PROTOTYPES, **LAB_PROTOTYPES) if lab else PROTOTYPES)
         if path is None:
             if lab:
                 _lab_lib = lib
@@ -1044,8 +1042,7 @@ atexit.register(_close_default_contexts)
 
 def default_context(device: int | None = None) -> HipContext:
     """Process-wide context for ``device`` (default: $LOCAL_RANK or 0)."""
-    if device is None:
-        device = int(os.environ.get("GSUM_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    device = resolve_device(device)
     ctx = _default_ctx.get(device)
     if ctx is None or ctx._h is None:
         ctx = HipContext(device)
@@ -1056,8 +1053,7 @@ def default_context(device: int | None = None) -> HipContext:
 def lab_context(device: int | None = None) -> HipContext:
     """Process-wide context on the LAB build of the library (libgsum_hip_lab.so: include/gsum_hip_debug.h's diagnostics, probes and
     schedule switches on top of the product ABI).  A context of its own -- streams, workspaces -- beside ``default_context``'s."""
-    if device is None:
-        device = int(os.environ.get("GSUM_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    device = resolve_device(device)
     ctx = _lab_ctx.get(device)
     if ctx is None or ctx._h is None:
         ctx = HipContext(device, lab=True)

@@ -6,6 +6,9 @@ import os
 
 import numpy as np
 
+from . import _sidelib
+from ._sidelib import DeviceHandle, _d, _i64
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsum_refdist.so")
 
@@ -23,33 +26,14 @@ PROTOTYPES = {
 }
 PHASES = ("h2d", "transpose", "column_sort", "percentiles", "coverage", "d2h")
 
-_lib = None
-
 
 def load_library(path: str | None = None):
     """dlopen libgsum_refdist.so and attach the prototypes.  Raises if it is absent (``python -m gsum_amd.build`` builds it)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise RuntimeError(f"{p} is missing: build it with `python -m gsum_amd.build`")
-    lib = C.CDLL(p)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    if path is None:
-        _lib = lib
-    return lib
-
-
-def _d(a):
-    return a.ctypes.data_as(_dp) if a is not None else None
+    return _sidelib.load(LIB_PATH, PROTOTYPES, path)
 
 
 def _check(lib, rc):
-    if rc:
-        raise ValueError(lib.gsum_refdist_last_error().decode())
+    _sidelib.check(lib, rc, "gsum_refdist_last_error")
 
 
 def _matrix(a, name):
@@ -59,11 +43,12 @@ def _matrix(a, name):
     return a
 
 
-class DeviceRefDist:
+class DeviceRefDist(DeviceHandle):
     """One n x m matrix resident on the device (uploaded once) and the operations of include/gsum_refdist.h on it."""
 
+    _free = "gsum_refdist_free"
+
     def __init__(self, device, A):
-        self._h = None
         self._lib = lib = load_library()
         A = _matrix(A, "A")
         self.n, self.m = A.shape
@@ -103,7 +88,7 @@ class DeviceRefDist:
             raise ValueError(f"lower and upper must both be (K, {self.n}), got {lower.shape} and {upper.shape}")
         K = lower.shape[0]
         counts = np.zeros((self.m, K), dtype=np.int64)
-        _check(self._lib, self._lib.gsum_refdist_coverage(self._handle(), _d(lower), _d(upper), K, counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        _check(self._lib, self._lib.gsum_refdist_coverage(self._handle(), _d(lower), _d(upper), K, _i64(counts)))
         return counts
 
     def times(self, reset=False):
@@ -111,20 +96,3 @@ class DeviceRefDist:
         ms = np.zeros(len(PHASES))
         _check(self._lib, self._lib.gsum_refdist_times(self._handle(), _d(ms), int(bool(reset))))
         return dict(zip(PHASES, ms.tolist()))
-
-    def free(self):
-        if getattr(self, "_h", None) is not None:
-            self._lib.gsum_refdist_free(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass

@@ -6,6 +6,9 @@ import os
 
 import numpy as np
 
+from . import _sidelib
+from ._sidelib import DeviceHandle, _d, _i32, _i64
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgsum_vario.so")
 
@@ -20,42 +23,21 @@ PROTOTYPES = {
     "gsum_vario_free": (None, [_p]),
 }
 
-_lib = None
-
 
 def load_library(path: str | None = None):
     """dlopen libgsum_vario.so and attach the prototypes.  Raises if it is absent (``python -m gsum_amd.build`` builds it)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise RuntimeError(f"{p} is missing: build it with `python -m gsum_amd.build`")
-    lib = C.CDLL(p)
-    for name, (res, args) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    if path is None:
-        _lib = lib
-    return lib
-
-
-def _d(a):
-    return a.ctypes.data_as(_dp)
-
-
-def _i32(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+    return _sidelib.load(LIB_PATH, PROTOTYPES, path)
 
 
 def _check(lib, rc):
-    if rc:
-        raise ValueError(lib.gsum_vario_last_error().decode())
+    _sidelib.check(lib, rc, "gsum_vario_last_error")
 
 
-class DeviceVariogram:
+class DeviceVariogram(DeviceHandle):
     """The device object of one (X, z, bounds): the pair stage runs in the constructor; ``counts``, ``h_sum`` (Nb,) and ``dij_sum``
     (Nb, n_curves) are its per-bin integer counts and sums."""
+
+    _free = "gsum_vario_free"
 
     def __init__(self, device, X, Z, bounds):
         self._lib = lib = load_library()
@@ -71,7 +53,7 @@ class DeviceVariogram:
         self.n_curves = nc
         h = C.c_void_p()
         _check(lib, lib.gsum_vario_create(int(device), _d(X), n, d, _d(Z), nc, _d(bounds), bounds.shape[0], C.byref(h),
-                                          self.counts.ctypes.data_as(C.POINTER(C.c_int64)), _d(self.h_sum), _d(self.dij_sum)))
+                                          _i64(self.counts), _d(self.h_sum), _d(self.dij_sum)))
         self._h = h
 
     def cov_sums(self, gamma_tilde, var_factor, corr_factor, bin1, bin2):
@@ -85,11 +67,6 @@ class DeviceVariogram:
         _check(self._lib, self._lib.gsum_vario_cov(self._h, _d(gt), float(var_factor), float(corr_factor), _i32(b1), _i32(b2),
                                                    b1.shape[0], _d(out)))
         return out
-
-    def free(self):
-        if getattr(self, "_h", None) is not None:
-            self._lib.gsum_vario_free(self._h)
-            self._h = None
 
 
 def device_corr(rho, corr_factor, device=0):

@@ -10,6 +10,7 @@
                         dependency list and up-to-date check.
 ``libgsum_refdist.so``  the reference distributions of GraphicalDiagnostic (include/gsum_refdist.h): column sort, row percentiles,
                         interval coverage.  Its own small library, built like the variogram's.
+The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations
 
@@ -28,14 +29,14 @@ HOST_PARTS = ("context", "gemm", "matrices", "potrf", "api_context", "api_operat
 DEPS += [os.path.join(HERE, "csrc", "host", f"{p}.hip.h") for p in HOST_PARTS]
 OUT = os.path.join(HERE, "libgsum_hip.so")
 OUT_LAB = os.path.join(HERE, "libgsum_hip_lab.so")
-VARIO_SRC = os.path.join(HERE, "csrc", "gsum_vario.hip")
-VARIO_MAP = os.path.join(HERE, "csrc", "gsum_vario.map")                 # linker version script: only gsum_vario_* exported
-VARIO_DEPS = [VARIO_SRC, VARIO_MAP, os.path.join(HERE, "csrc", "kernels", "variogram.hip.h"), os.path.join(ROOT, "include", "gsum_vario.h")]
-OUT_VARIO = os.path.join(HERE, "libgsum_vario.so")
-REFDIST_SRC = os.path.join(HERE, "csrc", "gsum_refdist.hip")
-REFDIST_MAP = os.path.join(HERE, "csrc", "gsum_refdist.map")             # linker version script: only gsum_refdist_* exported
-REFDIST_DEPS = [REFDIST_SRC, REFDIST_MAP, os.path.join(HERE, "csrc", "kernels", "refdist.hip.h"), os.path.join(ROOT, "include", "gsum_refdist.h")]
-OUT_REFDIST = os.path.join(HERE, "libgsum_refdist.so")
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
+               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc")]
+SIDE_SCAFFOLD = os.path.join(HERE, "csrc", "host", "sidelib.hip.h")      # the host scaffold every side library includes
+# name -> (source, linker version script: only gsum_<name>_* exported, kernel header, public header, output)
+SIDE = {name: (os.path.join(HERE, "csrc", f"gsum_{name}.hip"), os.path.join(HERE, "csrc", f"gsum_{name}.map"),
+               os.path.join(HERE, "csrc", "kernels", f"{kernels}.hip.h"), os.path.join(ROOT, "include", f"gsum_{name}.h"),
+               os.path.join(HERE, f"libgsum_{name}.so"))
+        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"))}
 
 
 def hipcc_path():
@@ -49,40 +50,34 @@ def up_to_date(out=OUT, deps=None):
     return os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(d) for d in (DEPS if deps is None else deps))
 
 
-def build_vario(force: bool = False, verbose: bool = False) -> str:
-    """libgsum_vario.so: the product's hipcc flags, only gsum_vario_* exported."""
-    if not force and up_to_date(OUT_VARIO, VARIO_DEPS):
-        return OUT_VARIO
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"), "-Wl,--version-script=" + VARIO_MAP, "-o", OUT_VARIO, VARIO_SRC]
+def build_side(name: str, force: bool = False, verbose: bool = False) -> str:
+    """libgsum_<name>.so: the product's hipcc flags, only gsum_<name>_* exported."""
+    src, vmap, kernels, header, out = SIDE[name]
+    if not force and up_to_date(out, [src, vmap, kernels, header, SIDE_SCAFFOLD]):
+        return out
+    cmd = [hipcc_path()] + HIPCC_FLAGS + ["-Wl,--version-script=" + vmap, "-o", out, src]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    return OUT_VARIO
+    return out
+
+
+def build_vario(force: bool = False, verbose: bool = False) -> str:
+    return build_side("vario", force, verbose)
 
 
 def build_refdist(force: bool = False, verbose: bool = False) -> str:
-    """libgsum_refdist.so: the product's hipcc flags, only gsum_refdist_* exported."""
-    if not force and up_to_date(OUT_REFDIST, REFDIST_DEPS):
-        return OUT_REFDIST
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc"), "-Wl,--version-script=" + REFDIST_MAP, "-o", OUT_REFDIST,
-           REFDIST_SRC]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    return OUT_REFDIST
+    return build_side("refdist", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
     out = OUT_LAB if lab else OUT
     if not lab:
-        build_vario(force=force, verbose=verbose)
-        build_refdist(force=force, verbose=verbose)
+        for name in SIDE:
+            build_side(name, force, verbose)
     if not force and up_to_date(out):
         return out
-    cmd = [hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(HERE, "csrc")] + (["-DGSUM_LAB"] if lab else []) + ["-o", out, SRC]
+    cmd = [hipcc_path()] + HIPCC_FLAGS + (["-DGSUM_LAB"] if lab else []) + ["-o", out, SRC]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
@@ -91,7 +86,7 @@ def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
-    print(OUT_VARIO)
-    print(OUT_REFDIST)
+    for side in SIDE.values():
+        print(side[-1])
     if "--lab" in sys.argv:
         print(build(force="--force" in sys.argv, verbose=True, lab=True))

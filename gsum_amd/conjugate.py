@@ -15,7 +15,6 @@ There is no CPU fallback; an unsupported kernel / option raises.
 """
 from __future__ import annotations
 
-import os
 import warnings
 
 import numpy as np
@@ -26,6 +25,7 @@ from sklearn.base import clone
 from sklearn.exceptions import ConvergenceWarning
 from sklearn.utils import check_random_state
 
+from ._backend import resolve_backend
 from ._lib import GSUM_MAX_RHS, default_context
 from .kernels import default_kernel, describe_gradient, describe_gradients, describe_kernel, describe_thetas
 
@@ -278,9 +278,7 @@ class ConjugateGaussianProcess:
         self.device = device
         # 'hip' (default; also through GSUM_BACKEND): libgsum_hip.so on an MI355X, loud failure without it.  'cpu': the same
         # operator interface on numpy / scipy / scikit-learn (gsum_amd/_cpu.py; BASELINE config 1) -- only when asked for
-        self.backend = backend if backend is not None else os.environ.get("GSUM_BACKEND", "hip")
-        if self.backend not in ("hip", "cpu"):
-            raise ValueError("backend must be 'hip' or 'cpu'")
+        self.backend = resolve_backend(backend)
         self.batch_restarts = True   # multi-start fits advance in lock step, objective evaluations batched on the device
         self._ctx = None
         self._L_dev = None          # device-resident Cholesky factor of kernel_(X_train_) + nugget

@@ -1,14 +1,10 @@
 // libgsum_refdist.so: the C ABI of include/gsum_refdist.h (reference distributions).  Kernels: kernels/refdist.hip.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <stdexcept>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "gsum_refdist.h"
+#include "host/sidelib.hip.h"
 #include "kernels/refdist.hip.h"
 
 #define GR_API extern "C" __attribute__((visibility("default")))
@@ -17,57 +13,12 @@ static_assert(gr::kSortLds == GSUM_REFDIST_LDS_SORT_MAX, "the header documents t
 
 namespace {
 
-thread_local std::string g_error;
-
-struct Error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define GR_CHECK(call) check((call), #call)
-#define GR_LAUNCHED(name) check(hipGetLastError(), name)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void reserve(size_t count) {                 // grow-only
-        if (count <= n) return;
-        release();
-        GR_CHECK(hipMalloc(&p, count * sizeof(T)));
-        n = count;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
-
-template <class F>
-int guarded(F&& f) {
-    try {
-        f();
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-    } catch (...) {
-        g_error = "unknown error";
-    }
-    return 1;
-}
-
 enum Phase { kH2D = 0, kTranspose, kColSort, kPercentiles, kCoverage, kD2H, kPhases };
 
 }  // namespace
 
-struct gsum_refdist {
-    int device = 0;
+struct gsum_refdist : Handle {
     int64_t n = 0, m = 0;
-    hipStream_t stream = nullptr;
     DevBuf<double> D, T;                           // the matrix (n x m) and the scratch matrix of the same size
     DevBuf<uint64_t> k0, k1;                       // long segments: the keys of every padded segment, ping and pong
     DevBuf<double> lower, upper, gamma, out;
@@ -81,7 +32,6 @@ struct gsum_refdist {
             (void)hipEventDestroy(e.second.first);
             (void)hipEventDestroy(e.second.second);
         }
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 
@@ -91,15 +41,15 @@ namespace {
 template <class F>
 void timed(gsum_refdist* h, Phase ph, F&& f) {
     hipEvent_t a = nullptr, b = nullptr;
-    GR_CHECK(hipEventCreate(&a));
+    SL_CHECK(hipEventCreate(&a));
     if (hipEventCreate(&b) != hipSuccess) {
         (void)hipEventDestroy(a);
         throw Error("hipEventCreate failed");
     }
     h->pending.push_back({(int)ph, {a, b}});
-    GR_CHECK(hipEventRecord(a, h->stream));
+    SL_CHECK(hipEventRecord(a, h->stream));
     f();
-    GR_CHECK(hipEventRecord(b, h->stream));
+    SL_CHECK(hipEventRecord(b, h->stream));
 }
 
 void settle(gsum_refdist* h) {
@@ -117,7 +67,7 @@ void settle(gsum_refdist* h) {
 // A call that throws between timed() and settle() must still drain the stream before its buffers can be touched again.
 template <class F>
 void run(gsum_refdist* h, F&& f) {
-    GR_CHECK(hipSetDevice(h->device));
+    SL_CHECK(hipSetDevice(h->device));
     try {
         f();
         settle(h);
@@ -133,7 +83,7 @@ void run(gsum_refdist* h, F&& f) {
 void transpose(gsum_refdist* h, const double* in, int64_t rows, int64_t cols, double* out) {
     const int64_t tiles = ((rows + gr::kTile - 1) / gr::kTile) * ((cols + gr::kTile - 1) / gr::kTile);
     gr::k_transpose<<<(unsigned)tiles, gr::kThreads, 0, h->stream>>>(in, rows, cols, out);
-    GR_LAUNCHED("k_transpose");
+    SL_LAUNCHED("k_transpose");
 }
 
 int pow2_at_least(int64_t v) {
@@ -154,8 +104,8 @@ void reserve_sort(gsum_refdist* h, int64_t nseg, int64_t len) {
 // dst segment s (dst + s * len) = src segment s sorted ascending, s < nseg; dst may be src.  reserve_sort() first.
 void sort_segments(gsum_refdist* h, const double* src, double* dst, int64_t nseg, int64_t len) {
     if (!h->lds_attr) {
-        GR_CHECK(hipFuncSetAttribute((const void*)gr::k_sort_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, gr::kSortLds * 8));
-        GR_CHECK(hipFuncSetAttribute((const void*)gr::k_sort_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, gr::kSortLds * 8));
+        SL_CHECK(hipFuncSetAttribute((const void*)gr::k_sort_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, gr::kSortLds * 8));
+        SL_CHECK(hipFuncSetAttribute((const void*)gr::k_sort_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, gr::kSortLds * 8));
         h->lds_attr = true;
     }
     hipStream_t st = h->stream;
@@ -163,24 +113,24 @@ void sort_segments(gsum_refdist* h, const double* src, double* dst, int64_t nseg
         const int P = pow2_at_least(len);
         const int threads = std::min(gr::kSortThreads, std::max(64, P / 2));
         gr::k_sort_lds<false><<<(unsigned)nseg, threads, (size_t)P * 8, st>>>(src, len, len, 1, P, dst, nullptr);
-        GR_LAUNCHED("k_sort_lds");
+        SL_LAUNCHED("k_sort_lds");
         return;
     }
     const int P = gr::kSortLds;
     const int64_t chunks = (len + P - 1) / P, Lp = chunks * P, total = nseg * Lp;
     if (nseg * chunks >= ((int64_t)1 << 31)) throw Error("gsum_refdist: too many sort chunks");
     gr::k_sort_lds<true><<<(unsigned)(nseg * chunks), gr::kSortThreads, (size_t)P * 8, st>>>(src, len, len, (int)chunks, P, nullptr, h->k0.p);
-    GR_LAUNCHED("k_sort_lds");
+    SL_LAUNCHED("k_sort_lds");
     uint64_t *in = h->k0.p, *out = h->k1.p;
     const int64_t blocks = (total + gr::kThreads - 1) / gr::kThreads;
     for (int64_t w = P; w < Lp; w *= 2) {
         gr::k_merge_pass<<<(unsigned)blocks, gr::kThreads, 0, st>>>(in, out, Lp, w, total);
-        GR_LAUNCHED("k_merge_pass");
+        SL_LAUNCHED("k_merge_pass");
         std::swap(in, out);
     }
     const int64_t vals = nseg * len;
     gr::k_keys_to_double<<<(unsigned)((vals + gr::kThreads - 1) / gr::kThreads), gr::kThreads, 0, st>>>(in, Lp, len, len, vals, dst);
-    GR_LAUNCHED("k_keys_to_double");
+    SL_LAUNCHED("k_keys_to_double");
 }
 
 void enqueue_sort_columns(gsum_refdist* h, double* sorted) {
@@ -189,7 +139,7 @@ void enqueue_sort_columns(gsum_refdist* h, double* sorted) {
     timed(h, kTranspose, [&] { transpose(h, h->D.p, n, m, h->T.p); });
     timed(h, kColSort, [&] { sort_segments(h, h->T.p, h->T.p, m, n); });
     timed(h, kTranspose, [&] { transpose(h, h->T.p, m, n, h->D.p); });
-    if (sorted) timed(h, kD2H, [&] { GR_CHECK(hipMemcpyAsync(sorted, h->D.p, sizeof(double) * n * m, hipMemcpyDeviceToHost, h->stream)); });
+    if (sorted) timed(h, kD2H, [&] { SL_CHECK(hipMemcpyAsync(sorted, h->D.p, sizeof(double) * n * m, hipMemcpyDeviceToHost, h->stream)); });
 }
 
 // Everything the percentile stage allocates; called before the first launch of the call.
@@ -206,15 +156,15 @@ void enqueue_row_percentiles(gsum_refdist* h, const std::vector<int64_t>& idx, c
     const int nq = (int)idx.size();
     hipStream_t st = h->stream;
     timed(h, kH2D, [&] {
-        GR_CHECK(hipMemcpyAsync(h->idx.p, idx.data(), sizeof(int64_t) * nq, hipMemcpyHostToDevice, st));
-        GR_CHECK(hipMemcpyAsync(h->gamma.p, gamma.data(), sizeof(double) * nq, hipMemcpyHostToDevice, st));
+        SL_CHECK(hipMemcpyAsync(h->idx.p, idx.data(), sizeof(int64_t) * nq, hipMemcpyHostToDevice, st));
+        SL_CHECK(hipMemcpyAsync(h->gamma.p, gamma.data(), sizeof(double) * nq, hipMemcpyHostToDevice, st));
     });
     timed(h, kPercentiles, [&] {
         sort_segments(h, h->D.p, h->T.p, n, m);
         gr::k_pick<<<(unsigned)((n + gr::kThreads - 1) / gr::kThreads), gr::kThreads, 0, st>>>(h->T.p, n, m, h->idx.p, h->gamma.p, nq, h->out.p);
-        GR_LAUNCHED("k_pick");
+        SL_LAUNCHED("k_pick");
     });
-    timed(h, kD2H, [&] { GR_CHECK(hipMemcpyAsync(out, h->out.p, sizeof(double) * nq * n, hipMemcpyDeviceToHost, st)); });
+    timed(h, kD2H, [&] { SL_CHECK(hipMemcpyAsync(out, h->out.p, sizeof(double) * nq * n, hipMemcpyDeviceToHost, st)); });
 }
 
 // numpy's virtual index of the 'linear' method, (m - 1) * (q / 100), its floor and the remainder
@@ -243,21 +193,13 @@ GR_API int gsum_refdist_create(int32_t device, const double* A, int64_t n, int64
         if (!A) throw Error("gsum_refdist_create: null pointer argument");
         if (n < 1 || m < 1) throw Error("gsum_refdist_create: n and m must be >= 1, got " + std::to_string(n) + " x " + std::to_string(m));
         if (n > (((int64_t)1 << 31) - 1) / m) throw Error("gsum_refdist_create: n * m must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(m));
-        auto h = new gsum_refdist();
-        try {
-            h->device = device;
+        create(out, device, [&](gsum_refdist* h) {
             h->n = n;
             h->m = m;
-            GR_CHECK(hipSetDevice(device));
-            GR_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
             h->D.reserve((size_t)(n * m));
             h->T.reserve((size_t)(n * m));
-            run(h, [&] { timed(h, kH2D, [&] { GR_CHECK(hipMemcpyAsync(h->D.p, A, sizeof(double) * n * m, hipMemcpyHostToDevice, h->stream)); }); });
-        } catch (...) {
-            delete h;
-            throw;
-        }
-        *out = h;
+            run(h, [&] { timed(h, kH2D, [&] { SL_CHECK(hipMemcpyAsync(h->D.p, A, sizeof(double) * n * m, hipMemcpyHostToDevice, h->stream)); }); });
+        });
     });
 }
 
@@ -308,11 +250,11 @@ GR_API int gsum_refdist_coverage(gsum_refdist* h, const double* lower, const dou
             h->counts.reserve((size_t)m * K);
             hipStream_t st = h->stream;
             timed(h, kH2D, [&] {
-                GR_CHECK(hipMemcpyAsync(h->lower.p, lower, sizeof(double) * K * n, hipMemcpyHostToDevice, st));
-                GR_CHECK(hipMemcpyAsync(h->upper.p, upper, sizeof(double) * K * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->lower.p, lower, sizeof(double) * K * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->upper.p, upper, sizeof(double) * K * n, hipMemcpyHostToDevice, st));
             });
             timed(h, kCoverage, [&] {
-                GR_CHECK(hipMemsetAsync(h->counts.p, 0, sizeof(unsigned long long) * m * K, st));
+                SL_CHECK(hipMemsetAsync(h->counts.p, 0, sizeof(unsigned long long) * m * K, st));
                 // slices of the points so that about 1024 workgroups exist; a slice is a whole number of LDS stages
                 const int64_t jb = (m + gr::kThreads - 1) / gr::kThreads, kb = (K + gr::kCovK - 1) / gr::kCovK;
                 const int64_t stages = (n + gr::kCovI - 1) / gr::kCovI;
@@ -322,9 +264,9 @@ GR_API int gsum_refdist_coverage(gsum_refdist* h, const double* lower, const dou
                 if (jb >= ((int64_t)1 << 31)) throw Error("gsum_refdist_coverage: too many curves");
                 gr::k_coverage<<<dim3((unsigned)jb, (unsigned)kb, (unsigned)slices), gr::kThreads, 0, st>>>(h->D.p, n, m, h->lower.p, h->upper.p, K,
                                                                                                              slice, h->counts.p);
-                GR_LAUNCHED("k_coverage");
+                SL_LAUNCHED("k_coverage");
             });
-            timed(h, kD2H, [&] { GR_CHECK(hipMemcpyAsync(counts, h->counts.p, sizeof(int64_t) * m * K, hipMemcpyDeviceToHost, st)); });
+            timed(h, kD2H, [&] { SL_CHECK(hipMemcpyAsync(counts, h->counts.p, sizeof(int64_t) * m * K, hipMemcpyDeviceToHost, st)); });
         });
     });
 }
@@ -339,9 +281,4 @@ GR_API int gsum_refdist_times(gsum_refdist* h, double* ms, int32_t reset) {
     });
 }
 
-GR_API void gsum_refdist_free(gsum_refdist* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-}
+GR_API void gsum_refdist_free(gsum_refdist* h) { destroy(h); }

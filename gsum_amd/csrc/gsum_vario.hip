@@ -1,85 +1,30 @@
 // libgsum_vario.so: the C ABI of include/gsum_vario.h (the empirical variogram).  Kernels: kernels/variogram.hip.h.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
 #include "gsum_vario.h"
+#include "host/sidelib.hip.h"
 #include "kernels/variogram.hip.h"
 
 #define GV_API extern "C" __attribute__((visibility("default")))
 
-namespace {
-
-thread_local std::string g_error;
-
-struct Error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw Error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define GV_CHECK(call) check((call), #call)
-#define GV_LAUNCHED(name) check(hipGetLastError(), name)
-
 template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void alloc(size_t count) {
-        release();
-        if (count) GV_CHECK(hipMalloc(&p, count * sizeof(T)));
-        n = count;
-    }
-    void reserve(size_t count) {                 // grow-only (cov's tile buffers)
-        if (count > n) alloc(std::max(count, n + n / 2));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~DevBuf() { release(); }
-};
+using GrowBuf = DevBuf<T, true>;                    // the cov stage's buffers: reserve() grows them by at least half
 
-template <class F>
-int guarded(F&& f) {
-    try {
-        f();
-        return 0;
-    } catch (const std::exception& e) {
-        g_error = e.what();
-    } catch (...) {
-        g_error = "unknown error";
-    }
-    return 1;
-}
-
-}  // namespace
-
-struct gsum_vario {
-    int device = 0;
+struct gsum_vario : Handle {
     int n = 0, d = 0, nc = 0, nbin = 0;
     int64_t P = 0;
-    hipStream_t stream = nullptr;
     std::vector<int64_t> counts;
     std::vector<int32_t> start;                    // Nb + 1 list offsets
     DevBuf<int16_t> T;                              // n x n bins
     DevBuf<uint32_t> pairs;                         // (i << 16) | j, grouped by bin, tril order within a bin
     // cov-stage buffers
-    DevBuf<gv::Tile> tiles;
-    DevBuf<int32_t> order, tstart;
-    DevBuf<double> gam, den, sq, slab, out;
+    GrowBuf<gv::Tile> tiles;
+    GrowBuf<int32_t> order, tstart;
+    GrowBuf<double> gam, den, sq, slab, out;
     std::vector<int32_t> last_b1, last_b2;         // the request list whose tiles, order and tstart are on the device
     int last_ntiles = 0;
-    ~gsum_vario() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 GV_API const char* gsum_vario_last_error(void) { return g_error.c_str(); }
@@ -99,16 +44,12 @@ GV_API int gsum_vario_create(int32_t device, const double* X, int64_t n, int32_t
             if (!std::isfinite(bounds[k])) throw Error("gsum_vario_create: bin bounds must be finite");
             if (k && bounds[k] < bounds[k - 1]) throw Error("gsum_vario_create: bin bounds must be non-decreasing");
         }
-        auto v = new gsum_vario();
-        try {
-            v->device = device;
+        create(out, device, [&](gsum_vario* v) {
             v->n = (int)n;
             v->d = d;
             v->nc = n_curves;
             v->nbin = n_bounds + 1;
             v->P = n * (n - 1) / 2;
-            GV_CHECK(hipSetDevice(device));
-            GV_CHECK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
             hipStream_t st = v->stream;
             const int nbin = v->nbin;
             DevBuf<double> dX, dZ, dB, dh, ddij;
@@ -128,21 +69,21 @@ GV_API int gsum_vario_create(int32_t device, const double* X, int64_t n, int32_t
             const int64_t nchunks = P ? (P + chunk - 1) / chunk : 0;
             dcnt.alloc((size_t)std::max<int64_t>(nchunks, 1) * nbin);
             v->pairs.alloc((size_t)std::max<int64_t>(P, 1));
-            GV_CHECK(hipMemcpyAsync(dX.p, X, sizeof(double) * n * d, hipMemcpyHostToDevice, st));
-            GV_CHECK(hipMemcpyAsync(dZ.p, Z, sizeof(double) * n_curves * n, hipMemcpyHostToDevice, st));
-            GV_CHECK(hipMemcpyAsync(dB.p, bounds, sizeof(double) * n_bounds, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(dX.p, X, sizeof(double) * n * d, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(dZ.p, Z, sizeof(double) * n_curves * n, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(dB.p, bounds, sizeof(double) * n_bounds, hipMemcpyHostToDevice, st));
             gv::k_bin_table<<<dim3((unsigned)((n + 63) / 64), (unsigned)((n + 3) / 4)), gv::kThreads, 0, st>>>(dX.p, (int)n, d, dB.p, n_bounds, v->T.p);
-            GV_LAUNCHED("k_bin_table");
+            SL_LAUNCHED("k_bin_table");
             v->counts.assign(nbin, 0);
             v->start.assign(nbin + 1, 0);
             std::vector<int> cnt;                               // host staging of the compaction: outlives the stream's last copy
             if (P) {
-                GV_CHECK(hipMemsetAsync(dcnt.p, 0, sizeof(int) * nchunks * nbin, st));
+                SL_CHECK(hipMemsetAsync(dcnt.p, 0, sizeof(int) * nchunks * nbin, st));
                 gv::k_pair_count<<<(unsigned)nchunks, gv::kThreads, 0, st>>>(v->T.p, (int)n, P, chunk, nbin, dcnt.p);
-                GV_LAUNCHED("k_pair_count");
+                SL_LAUNCHED("k_pair_count");
                 cnt.resize((size_t)nchunks * nbin);
-                GV_CHECK(hipMemcpyAsync(cnt.data(), dcnt.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, st));
-                GV_CHECK(hipStreamSynchronize(st));
+                SL_CHECK(hipMemcpyAsync(cnt.data(), dcnt.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipStreamSynchronize(st));
                 for (int64_t c = 0; c < nchunks; ++c)
                     for (int b = 0; b < nbin; ++b) v->counts[b] += cnt[(size_t)c * nbin + b];
                 for (int b = 0; b < nbin; ++b) v->start[b + 1] = (int32_t)(v->start[b] + v->counts[b]);
@@ -154,19 +95,19 @@ GV_API int gsum_vario_create(int32_t device, const double* X, int64_t n, int32_t
                         cnt[(size_t)c * nbin + b] = run[b];
                         run[b] += k;
                     }
-                GV_CHECK(hipMemcpyAsync(dcnt.p, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice, st));
-                GV_CHECK(hipMemcpyAsync(dstart.p, v->start.data(), sizeof(int) * (nbin + 1), hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(dcnt.p, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(dstart.p, v->start.data(), sizeof(int) * (nbin + 1), hipMemcpyHostToDevice, st));
                 gv::k_pair_scatter<<<(unsigned)nchunks, gv::kThreads, 0, st>>>(v->T.p, (int)n, P, chunk, nbin, dcnt.p, v->pairs.p);
-                GV_LAUNCHED("k_pair_scatter");
+                SL_LAUNCHED("k_pair_scatter");
                 gv::k_bin_sums<<<(unsigned)nbin, gv::kThreads, 0, st>>>(dX.p, (int)n, d, dZ.p, n_curves, v->pairs.p, dstart.p, dh.p, ddij.p);
-                GV_LAUNCHED("k_bin_sums");
-                GV_CHECK(hipMemcpyAsync(h_sum, dh.p, sizeof(double) * nbin, hipMemcpyDeviceToHost, st));
-                GV_CHECK(hipMemcpyAsync(dij_sum, ddij.p, sizeof(double) * nbin * n_curves, hipMemcpyDeviceToHost, st));
+                SL_LAUNCHED("k_bin_sums");
+                SL_CHECK(hipMemcpyAsync(h_sum, dh.p, sizeof(double) * nbin, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(dij_sum, ddij.p, sizeof(double) * nbin * n_curves, hipMemcpyDeviceToHost, st));
             } else {
                 std::fill(h_sum, h_sum + nbin, 0.0);
                 std::fill(dij_sum, dij_sum + (size_t)nbin * n_curves, 0.0);
             }
-            GV_CHECK(hipStreamSynchronize(st));
+            SL_CHECK(hipStreamSynchronize(st));
             std::copy(v->counts.begin(), v->counts.end(), counts);
             // the cov stage's buffers, sized for one request per bin (compute()) with up to 4 curves per group
             int64_t tiles = 0;
@@ -183,11 +124,7 @@ GV_API int gsum_vario_create(int32_t device, const double* X, int64_t n, int32_t
             v->den.reserve((size_t)nbin * ncp);
             v->sq.reserve((size_t)nbin * ncp);
             v->out.reserve((size_t)nbin * n_curves);
-        } catch (...) {
-            delete v;
-            throw;
-        }
-        *out = v;
+        });
     });
 }
 
@@ -198,7 +135,7 @@ void launch_cov(gsum_vario* v, int ntiles, int groups, int ncp, double corr_fact
     const size_t lds = (size_t)v->nbin * CG <= (size_t)gv::kGammaLds ? sizeof(double) * v->nbin * CG : 0;   // gamma~ in LDS when it fits
     gv::k_cov<CG><<<dim3((unsigned)ntiles, (unsigned)groups), gv::kThreads, lds, v->stream>>>(
         v->tiles.p, v->order.p, v->pairs.p, v->T.p, v->n, v->gam.p, v->nbin, v->den.p, v->sq.p, ncp, corr_factor, v->slab.p);
-    GV_LAUNCHED("k_cov");
+    SL_LAUNCHED("k_cov");
 }
 
 }  // namespace
@@ -213,7 +150,7 @@ GV_API int gsum_vario_cov(gsum_vario* v, const double* gamma_tilde, double var_f
             if (bin1[r] < 0 || bin1[r] >= nbin || bin2[r] < 0 || bin2[r] >= nbin)
                 throw Error("gsum_vario_cov: bin index out of range [0, " + std::to_string(nbin) + ")");
         if (n_pairs == 0) return;
-        GV_CHECK(hipSetDevice(v->device));
+        SL_CHECK(hipSetDevice(v->device));
         const int CG = nc < 4 ? nc : 4;
         const int ncp = (nc + CG - 1) / CG * CG, groups = ncp / CG;
         auto gt = [&](int b, int c) { return gamma_tilde[(size_t)b * nc + (c < nc ? c : 0)]; };   // padded curves repeat curve 0
@@ -275,14 +212,14 @@ GV_API int gsum_vario_cov(gsum_vario* v, const double* gamma_tilde, double var_f
         hipStream_t st = v->stream;
         if (!cached) {
             if (ntiles) {
-                GV_CHECK(hipMemcpyAsync(v->tiles.p, tiles.data(), sizeof(gv::Tile) * ntiles, hipMemcpyHostToDevice, st));
-                GV_CHECK(hipMemcpyAsync(v->order.p, order.data(), sizeof(int32_t) * ntiles, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(v->tiles.p, tiles.data(), sizeof(gv::Tile) * ntiles, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(v->order.p, order.data(), sizeof(int32_t) * ntiles, hipMemcpyHostToDevice, st));
             }
-            GV_CHECK(hipMemcpyAsync(v->tstart.p, tstart.data(), sizeof(int32_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(v->tstart.p, tstart.data(), sizeof(int32_t) * (n_pairs + 1), hipMemcpyHostToDevice, st));
         }
-        GV_CHECK(hipMemcpyAsync(v->gam.p, gam.data(), sizeof(double) * gam.size(), hipMemcpyHostToDevice, st));
-        GV_CHECK(hipMemcpyAsync(v->den.p, den.data(), sizeof(double) * den.size(), hipMemcpyHostToDevice, st));
-        GV_CHECK(hipMemcpyAsync(v->sq.p, sq.data(), sizeof(double) * sq.size(), hipMemcpyHostToDevice, st));
+        SL_CHECK(hipMemcpyAsync(v->gam.p, gam.data(), sizeof(double) * gam.size(), hipMemcpyHostToDevice, st));
+        SL_CHECK(hipMemcpyAsync(v->den.p, den.data(), sizeof(double) * den.size(), hipMemcpyHostToDevice, st));
+        SL_CHECK(hipMemcpyAsync(v->sq.p, sq.data(), sizeof(double) * sq.size(), hipMemcpyHostToDevice, st));
         if (ntiles) {
             if (CG == 1) launch_cov<1>(v, ntiles, groups, ncp, corr_factor);
             else if (CG == 2) launch_cov<2>(v, ntiles, groups, ncp, corr_factor);
@@ -291,9 +228,9 @@ GV_API int gsum_vario_cov(gsum_vario* v, const double* gamma_tilde, double var_f
         }
         const int nout = n_pairs * nc;
         gv::k_cov_reduce<<<(unsigned)((nout + gv::kThreads - 1) / gv::kThreads), gv::kThreads, 0, st>>>(v->slab.p, v->tstart.p, n_pairs, nc, ncp, v->out.p);
-        GV_LAUNCHED("k_cov_reduce");
-        GV_CHECK(hipMemcpyAsync(sums, v->out.p, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
-        GV_CHECK(hipStreamSynchronize(st));
+        SL_LAUNCHED("k_cov_reduce");
+        SL_CHECK(hipMemcpyAsync(sums, v->out.p, sizeof(double) * nout, hipMemcpyDeviceToHost, st));
+        SL_CHECK(hipStreamSynchronize(st));
         if (!cached) {
             v->last_b1.assign(bin1, bin1 + n_pairs);
             v->last_b2.assign(bin2, bin2 + n_pairs);
@@ -306,21 +243,16 @@ GV_API int gsum_vario_corr(int32_t device, const double* rho, int64_t m, double 
     return guarded([&] {
         if (m < 0 || (m && (!rho || !out))) throw Error("gsum_vario_corr: bad arguments");
         if (!m) return;
-        GV_CHECK(hipSetDevice(device));
+        SL_CHECK(hipSetDevice(device));
         DevBuf<double> dr, dout;
         dr.alloc(m);
         dout.alloc(m);
-        GV_CHECK(hipMemcpy(dr.p, rho, sizeof(double) * m, hipMemcpyHostToDevice));
+        SL_CHECK(hipMemcpy(dr.p, rho, sizeof(double) * m, hipMemcpyHostToDevice));
         gv::k_corr<<<(unsigned)((m + gv::kThreads - 1) / gv::kThreads), gv::kThreads>>>(dr.p, m, corr_factor, dout.p);
-        GV_LAUNCHED("k_corr");
-        GV_CHECK(hipMemcpy(out, dout.p, sizeof(double) * m, hipMemcpyDeviceToHost));
-        GV_CHECK(hipDeviceSynchronize());
+        SL_LAUNCHED("k_corr");
+        SL_CHECK(hipMemcpy(out, dout.p, sizeof(double) * m, hipMemcpyDeviceToHost));
+        SL_CHECK(hipDeviceSynchronize());
     });
 }
 
-GV_API void gsum_vario_free(gsum_vario* v) {
-    if (!v) return;
-    (void)hipSetDevice(v->device);
-    (void)hipStreamSynchronize(v->stream);
-    delete v;
-}
+GV_API void gsum_vario_free(gsum_vario* v) { destroy(v); }

@@ -16,20 +16,18 @@ eigen panels of ``GraphicalDiagnostic``).
 """
 from __future__ import annotations
 
-import os
 
 import numpy as np
 import scipy.stats as stats
 
+from ._backend import resolve_backend
 from ._lib import ChainAborted, default_context
 
 __all__ = ["Diagnostic", "pivoted_cholesky"]
 
 
 def _context(device, backend):
-    backend = backend if backend is not None else os.environ.get("GSUM_BACKEND", "hip")
-    if backend not in ("hip", "cpu"):
-        raise ValueError("backend must be 'hip' or 'cpu'")
+    backend = resolve_backend(backend)
     if backend == "cpu":
         from ._cpu import cpu_context
         return cpu_context(), backend

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .variogram import _resolve
+from ._backend import resolve_backend, resolve_device
 
 __all__ = ["sort_columns", "row_percentiles", "qq_bands", "interval_coverage", "device_matrix"]
 
@@ -38,15 +38,14 @@ def device_matrix(A, device=None):
     """A (n, m) uploaded to the device: the ``DeviceRefDist`` of _refdist_lib (``sort_columns``, ``row_percentiles``, ``qq_bands``,
     ``coverage``, ``times``, ``free``), for several operations on one upload."""
     from ._refdist_lib import DeviceRefDist
-    device, _ = _resolve(device, "hip")
-    return DeviceRefDist(device, _matrix(A, "A"))
+    return DeviceRefDist(resolve_device(device), _matrix(A, "A"))
 
 
 def sort_columns(A, device=None, backend=None):
     """Every column ascending: ``np.sort(A, axis=0)``, NaN last.  Bit-equal to numpy's for finite and infinite values (-0.0 and
     +0.0 compare equal and may come in either order; a NaN comes back positive)."""
     A = _matrix(A, "A")
-    device, backend = _resolve(device, backend)
+    backend = resolve_backend(backend)
     if backend == "cpu":
         return np.sort(A, axis=0)
     with device_matrix(A, device) as M:
@@ -57,7 +56,7 @@ def row_percentiles(A, q, device=None, backend=None):
     """``np.percentile(A, q, axis=1)`` (the default 'linear' method), shape (len(q), n); a row with a NaN gives NaN."""
     A = _matrix(A, "A")
     q = _percents(q)
-    device, backend = _resolve(device, backend)
+    backend = resolve_backend(backend)
     if backend == "cpu":
         return np.percentile(A, q, axis=1)
     with device_matrix(A, device) as M:
@@ -70,7 +69,7 @@ def qq_bands(E, q, return_sorted=False, device=None, backend=None):
     device."""
     E = _matrix(E, "E")
     q = _percents(q)
-    device, backend = _resolve(device, backend)
+    backend = resolve_backend(backend)
     if backend == "cpu":
         S = np.sort(E, axis=0)
         bands = np.percentile(S, q, axis=1)
@@ -90,7 +89,7 @@ def interval_coverage(Y, lower, upper, device=None, backend=None):
     n = Y.shape[0]
     if lower.shape != upper.shape or lower.shape[1] != n:
         raise ValueError(f"lower and upper must both be (K, {n}), got {lower.shape} and {upper.shape}")
-    device, backend = _resolve(device, backend)
+    backend = resolve_backend(backend)
     if backend == "cpu":
         return np.stack([np.average((lower < r) & (r < upper), axis=1) for r in Y.T])
     with device_matrix(Y, device) as M:

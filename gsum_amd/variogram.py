@@ -14,24 +14,16 @@ are the reference's host numpy / scipy code on ``gamma_tilde_grid``.
 """
 from __future__ import annotations
 
-import os
 from math import gamma
 
 import numpy as np
 from scipy.special import hyp2f1
 
+from ._backend import resolve_backend, resolve_device
+
 __all__ = ["VariogramFourthRoot"]
 
 _CHUNK = 1 << 20            # cpu backend: array elements per block
-
-
-def _resolve(device, backend):
-    backend = backend if backend is not None else os.environ.get("GSUM_BACKEND", "hip")
-    if backend not in ("hip", "cpu"):
-        raise ValueError("backend must be 'hip' or 'cpu'")
-    if device is None:
-        device = int(os.environ.get("GSUM_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-    return int(device), backend
 
 
 class VariogramFourthRoot:
@@ -57,7 +49,7 @@ class VariogramFourthRoot:
 
     def __init__(self, X, z, bin_bounds, device=None, backend=None):
         self._dev = None
-        self.device, self.backend = _resolve(device, backend)
+        self.backend, self.device = resolve_backend(backend), resolve_device(device)
         X = np.asarray(X, dtype=float)
         if X.ndim != 2:
             raise ValueError("X must have shape (n_samples, n_features)")
