@@ -10,6 +10,8 @@
                         dependency list and up-to-date check.
 ``libgsum_refdist.so``  the reference distributions of GraphicalDiagnostic (include/gsum_refdist.h): column sort, row percentiles,
                         interval coverage.  Its own small library, built like the variogram's.
+``libgsum_pointwise.so`` the grid log likelihood and the interval coverage of TruncationPointwise (include/gsum_pointwise.h).  Its own
+                        small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations
@@ -36,7 +38,7 @@ SIDE_SCAFFOLD = os.path.join(HERE, "csrc", "host", "sidelib.hip.h")      # the h
 SIDE = {name: (os.path.join(HERE, "csrc", f"gsum_{name}.hip"), os.path.join(HERE, "csrc", f"gsum_{name}.map"),
                os.path.join(HERE, "csrc", "kernels", f"{kernels}.hip.h"), os.path.join(ROOT, "include", f"gsum_{name}.h"),
                os.path.join(HERE, f"libgsum_{name}.so"))
-        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"))}
+        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"))}
 
 
 def hipcc_path():
@@ -68,6 +70,10 @@ def build_vario(force: bool = False, verbose: bool = False) -> str:
 
 def build_refdist(force: bool = False, verbose: bool = False) -> str:
     return build_side("refdist", force, verbose)
+
+
+def build_pointwise(force: bool = False, verbose: bool = False) -> str:
+    return build_side("pointwise", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:

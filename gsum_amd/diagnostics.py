@@ -11,7 +11,7 @@ default samples), with the reference's own arithmetic.
 ``GraphicalDiagnostic`` (graphical.py) owns a ``Diagnostic`` and puts its results beside reference distributions made by simulation;
 the band stage of those runs in libgsum_refdist.so (refdist.py).
 
-Not provided: ``TruncationPointwise`` and a device eigensolver (``eigen_errors`` runs on ``backend='cpu'`` only, and with it the
+``TruncationPointwise`` is pointwise.py.  Not provided: a device eigensolver (``eigen_errors`` runs on ``backend='cpu'`` only, and with it the
 eigen panels of ``GraphicalDiagnostic``).
 """
 from __future__ import annotations
