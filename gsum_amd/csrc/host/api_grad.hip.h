@@ -277,10 +277,11 @@ static int gs_grad_harvest(gsum_ctx* ctx, gs_slot* sl, int P, double* G_out, dou
     const int i = sl->pending, k = ctx->in->k;
     if (i < 0) return 0;
     if (gs_eval_harvest(ctx, sl, G_out, sld_out, info_out)) return -1;      // synchronises the stream
-    for (int p = 0; p < P; ++p) {
+    const bool ok = info_out[i] == 0;                  // not positive definite: no gradient pieces (the caller looks at info), as gs_grad_small
+    for (int p = 0; p < P; ++p) {                      // and gs_grad_batch_wave -- the stage ran on a factor that stops at the failing column
         for (int a = 0; a < k; ++a)
-            for (int b = 0; b < k; ++b) H_out[(((size_t)i * P + p) * k + a) * k + b] = sl->hgrad[(size_t)p * 257 + a * 16 + b];
-        trace_out[(size_t)i * P + p] = sl->hgrad[(size_t)p * 257 + 256];
+            for (int b = 0; b < k; ++b) H_out[(((size_t)i * P + p) * k + a) * k + b] = ok ? sl->hgrad[(size_t)p * 257 + a * 16 + b] : 0.0;
+        trace_out[(size_t)i * P + p] = ok ? sl->hgrad[(size_t)p * 257 + 256] : 0.0;
     }
     return 0;
 }
