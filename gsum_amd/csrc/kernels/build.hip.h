@@ -18,9 +18,12 @@
 // routine operation for operation (Tang-style: N = floor_{1/16}(x log2 e), two-step Cody-Waite
 // reduction, 16-entry 2^(j/16) table with tail, degree-6 polynomial, every step one IEEE fma), so
 // kernel-matrix entries come out bit-identical to sklearn's.  Checked bit-for-bit against np.exp on 13k
-// arguments by tests/test_exp_restatement.py (CPU) and on the device by tests/test_gpu_parity.py.
+// arguments by tests/test_exp_restatement.py (CPU) and on the device by tests/test_gpu_parity.py and
+// tests/test_gpu_build_classes.py.
 // |x| >= 707.7 (results below 4.6e-308 or overflow) takes SVML's scalar "rare" path on the host; here it
-// falls through to the device library's exp: such entries are < 1e-307 against a unit diagonal.
+// falls through to the device library's exp: such entries are < 1e-307 against a unit diagonal.  That band
+// (subnormal results) and the arguments beyond it (exactly zero) are checked entry by entry, on every
+// build path, by tests/test_gpu_build_classes.py.
 __device__ __constant__ double gs_exp_th[16] = {
     0x1.0000000000000p+0, 0x1.0b5586cf9890fp+0, 0x1.172b83c7d517bp+0, 0x1.2387a6e756238p+0,
     0x1.306fe0a31b715p+0, 0x1.3dea64c123422p+0, 0x1.4bfdad5362a27p+0, 0x1.5ab07dd485429p+0,

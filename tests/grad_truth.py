@@ -166,14 +166,17 @@ def _kernels():
 @dataclass(frozen=True)
 class Case:
     """One shape of the matrix.  ``expr``: the kernel over the names of ``_kernels`` with WHITE standing for the white-noise level of the
-    run; ``dup``: rows 0 and n // 2 (and row n - 1 where n > 2) of X coincide pairwise -- the den == 0 branch of Matern-1/2."""
-    path: str               # small_flat | small_tree | general_flat | general_tree
+    run; ``dup``: rows 0 and n // 2 (and row n - 1 where n > 2) of X coincide pairwise -- the den == 0 branch of Matern-1/2; ``grid``: X is
+    the uniform grid ``grid * arange(n)`` (d = 1) instead of random points -- wide enough in length scales that most exp arguments of
+    K_gradient lie in the subnormal band or beyond it (tests/build_classes.py)."""
+    path: str               # small_flat | small_tree | general_flat | general_tree | general_wide
     n: int
     d: int
     k: int
     expr: str
     dup: bool = False
     side: float = 0.0       # X is uniform on [0, side]^d; 0: 3 + 0.02 n for d = 1, 2.5 otherwise
+    grid: float = 0.0       # > 0: X = grid * arange(n)
 
     @property
     def id(self):
@@ -190,6 +193,9 @@ class Case:
         n, d, k = self.n, self.d, self.k
         side = self.side or ((3.0 + 0.02 * n) if d == 1 else 2.5)
         X = rng.rand(n, d) * side
+        if self.grid:
+            assert d == 1 and not self.dup
+            X = self.grid * np.arange(n, dtype=float)[:, None]
         pairs = []
         if self.dup and n >= 2:
             X[n // 2] = X[0]
@@ -257,6 +263,15 @@ CASES = [
     # ---- the general path, kernel trees: k_grad_contract<true, 1>
     Case("general_tree", 129, 1, 5, "Pow(C(1.1) * RQ(length_scale=1.2, alpha=0.7) + C(0.5), 2) + W(WHITE)"),
     Case("general_tree", 257, 2, 5, "C(0.6) * RBF([0.8, 1.2]) + C(0.05) * Dot(sigma_0=1.3) + W(WHITE)"),
+    # ---- the general path on wide uniform grids (the RBF and Matern-5/2 grids of tests/build_classes.py): dR_p is mostly exact zeros (exp
+    # argument below -745.2) and partly subnormal (the band down from -707.7), on 4 resp. 11 diagonals.  n = 278 and 488 are the smallest
+    # orders at which a tenth of the entries is in range, a tenth is far and a thousand lie in the band (test_build_classes_cpu.py).
+    # Inputs chosen for REF_LIMIT: these matrices are so well conditioned (cond_2(R) = 27 resp. 5 with an amplitude and white noise alone; the
+    # Matern grid's points are a length scale apart and no amplitude moves it past 14) that cond S no longer covers the plain einsum
+    # reference's ~100 eps S on the dense amplitude and noise parameters (7 resp. 21 eps).  The RBF case carries an additive constant
+    # (cond 3e2 on the tight run); the Matern case keeps the one parameter this is about, the length scale
+    Case("general_wide", 278, 1, 5, "C(1.3) * RBF(0.2) + W(WHITE) + C(0.5)", grid=0.05),
+    Case("general_wide", 488, 1, 5, "Matern(0.3, nu=2.5) + W(WHITE, noise_level_bounds='fixed')", grid=0.3),
 ]
 RUNS = [("tight", WHITE_TIGHT), ("amplified", WHITE_AMPLIFIED)]
 CASE_RUNS = [(c, run, w) for c in CASES for run, w in RUNS]
