@@ -1,5 +1,6 @@
 // libgsum_hip.so — host side of the C ABI declared in include/gsum_hip.h.
-// One context = one GPU = two HIP streams (main + high-priority panel stream for look-ahead).
+// One context = one GPU = four HIP streams on four command-processor pipes, created by gsum_init (host/api_context.hip.h): slot 0's main
+// (low priority), panel and auxiliary streams (high) and one more high-priority stream -- the chain streams of a batch's three groups.
 // the library is built with -fvisibility=hidden: what include/gsum_hip.h declares (and, in the lab build, gsum_hip_debug.h) is all it exports
 #pragma GCC visibility push(default)
 #include "gsum_hip.h"

@@ -14,9 +14,9 @@ static int gs_slot_init(gsum_ctx* ctx, gs_slot* sl) {
     else GS_CHECK(hipStreamCreateWithPriority(&sl->sm, hipStreamNonBlocking, ctx->prio_lo));
     GS_CHECK(hipEventCreateWithFlags(&sl->evFork, hipEventDisableTiming));
     for (int i = 0; i < 4; ++i) GS_CHECK(hipEventCreate(&sl->tev[i]));
-    GS_CHECK(hipMalloc((void**)&sl->dres, 258 * sizeof(double)));
+    GS_CHECK(hipMalloc((void**)&sl->dres, GS_RES_LEN * sizeof(double)));
     GS_CHECK(hipMalloc((void**)&sl->dinfo, sizeof(int)));
-    GS_CHECK(hipHostMalloc((void**)&sl->hres, 258 * sizeof(double), hipHostMallocDefault));
+    GS_CHECK(hipHostMalloc((void**)&sl->hres, GS_RES_LEN * sizeof(double), hipHostMallocDefault));
     return 0;
 }
 

@@ -24,7 +24,7 @@ static int gs_grad_check(gsum_ctx* ctx, const gsum_grad_param* params, int32_t n
 }
 
 // One evaluation with gradient pieces, enqueued on slot `sl` (ctx->cur); results land in the slot's pinned buffers (hres: the
-// fused evaluation's 258 doubles, hgrad: P x 257) when its main stream has drained.
+// fused evaluation's value record, hgrad: P gradient records) when its main stream has drained.
 //   solo: the single-evaluation schedule -- the U = L^-T sweep trails the look-ahead factorisation panel by panel on a stream
 //         of its own, V^T runs beside the SYRK on the panel stream;
 //  !solo: everything in order on the slot's main stream (a batch hides latencies with its other evaluations: gs_lml_on's rule).
@@ -51,15 +51,15 @@ static gs_grad_layout gs_grad_offsets(int64_t n, int64_t np, int P, bool split) 
     L.o_q = L.o_v + up((size_t)16 * ldg * 8);
     L.o_t = L.o_q + up((size_t)P * n * 16 * 8);
     L.o_o = L.o_t + up((size_t)P * n * 8);
-    L.o_p = L.o_o + up((size_t)P * 257 * 8);
-    L.o_d = L.o_p + up((size_t)P * L.chunks * 257 * 8);
+    L.o_p = L.o_o + up((size_t)P * GS_GRES_LEN * 8);
+    L.o_d = L.o_p + up((size_t)P * L.chunks * GS_GRES_LEN * 8);
     L.total = L.o_d + (split ? (size_t)P * up((size_t)np * ldg * 8) : 0);
     return L;
 }
 
 static int gs_grad_reserve(gsum_ctx* ctx, gs_slot* sl, int64_t n, int64_t np, int P, bool solo) {
     if (gs_reserve(ctx, &sl->gws, &sl->gws_cap, gs_grad_offsets(n, np, P, solo && ctx->grad_split).total)) return -1;
-    if (!sl->hgrad) GS_CHECK(hipHostMalloc((void**)&sl->hgrad, (size_t)GSUM_MAX_GRAD * 257 * sizeof(double), hipHostMallocDefault));
+    if (!sl->hgrad) GS_CHECK(hipHostMalloc((void**)&sl->hgrad, (size_t)GSUM_MAX_GRAD * GS_GRES_LEN * sizeof(double), hipHostMallocDefault));
     if (solo && !sl->su) {
         // the sweep runs beside the factorisation's main and panel streams: it takes the context's fourth stream (the third group's chain
         // stream of a batch, idle here) -- a stream created now would share a command-processor pipe with one of those two
@@ -267,22 +267,18 @@ static int gs_grad_post(gsum_ctx* ctx, gs_slot* sl, gsum_mat* m, const gsum_kern
     GS_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_grad_reduce2, dim3((unsigned)P), dim3(256), 0, s, part, chunks, dout);
     GS_CHECK(hipGetLastError());
-    GS_CHECK(hipMemcpyAsync(sl->hgrad, dout, (size_t)P * 257 * 8, hipMemcpyDeviceToHost, s));
+    GS_CHECK(hipMemcpyAsync(sl->hgrad, dout, (size_t)P * GS_GRES_LEN * 8, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
 // wait for the gradient evaluation pending on a slot (index sl->pending) and copy its pieces out
 static int gs_grad_harvest(gsum_ctx* ctx, gs_slot* sl, int P, double* G_out, double* sld_out, int64_t* info_out, double* trace_out,
                            double* H_out) {
-    const int i = sl->pending, k = ctx->in->k;
+    const int i = sl->pending;
     if (i < 0) return 0;
     if (gs_eval_harvest(ctx, sl, G_out, sld_out, info_out)) return -1;      // synchronises the stream
-    const bool ok = info_out[i] == 0;                  // not positive definite: no gradient pieces (the caller looks at info), as gs_grad_small
-    for (int p = 0; p < P; ++p) {                      // and gs_grad_batch_wave -- the stage ran on a factor that stops at the failing column
-        for (int a = 0; a < k; ++a)
-            for (int b = 0; b < k; ++b) H_out[(((size_t)i * P + p) * k + a) * k + b] = ok ? sl->hgrad[(size_t)p * 257 + a * 16 + b] : 0.0;
-        trace_out[(size_t)i * P + p] = ok ? sl->hgrad[(size_t)p * 257 + 256] : 0.0;
-    }
+    for (int p = 0; p < P; ++p)
+        gs_unpack_grad(sl->hgrad + (size_t)p * GS_GRES_LEN, info_out[i] == 0, ctx->in->k, P, (size_t)i, p, H_out, trace_out);
     return 0;
 }
 
@@ -301,7 +297,7 @@ static int gs_grad_small(gsum_ctx* ctx, const gsum_kernel_desc* descs, int n_des
     // descriptors and gradient parameters travel in ONE copy, results and gradient pieces come back in ONE (each copy of a pageable buffer is
     // ~10 us of a ~100-us call): [descs | params] and [res | gres] are contiguous on the device, offsets by the launch's count
     const size_t in_cap = (size_t)CH * (sizeof(gsum_kernel_desc) + (size_t)P * sizeof(gsum_grad_param));
-    const size_t out_cap = (size_t)CH * (258 + (size_t)P * 257) * 8;
+    const size_t out_cap = (size_t)CH * (GS_RES_LEN + (size_t)P * GS_GRES_LEN) * 8;
     const size_t o_in = 0, o_out = up(in_cap), o_scr = o_out + up(out_cap);
     if (gs_reserve(ctx, &ctx->scratch, &ctx->scratch_cap, o_scr + (size_t)CH * GS_GSMALL_SCRATCH * 8)) return -1;
     char* base = (char*)ctx->scratch;
@@ -313,32 +309,22 @@ static int gs_grad_small(gsum_ctx* ctx, const gsum_kernel_desc* descs, int n_des
         memcpy(stage, descs + lo, dbytes);
         memcpy(stage + dbytes, params + (size_t)lo * P, pbytes);
         GS_CHECK(hipMemcpyAsync(base + o_in, stage, dbytes + pbytes, hipMemcpyHostToDevice, s));
-        bool tree = false;
-        for (int e = 0; e < cnt; ++e) tree = tree || descs[lo + e].n_ops > 0;
+        const bool tree = gs_any_tree(descs + lo, cnt);
         double* dres = (double*)(base + o_out);
-        double* dgres = dres + (size_t)cnt * 258;
+        double* dgres = dres + (size_t)cnt * GS_RES_LEN;
         hipLaunchKernelGGL(tree ? k_grad_small<true> : k_grad_small<false>, dim3(cnt), dim3(256), 0, s, ctx->in->X, (int)ctx->in->n, ctx->in->d,
                            ctx->in->Z, k, (const gsum_kernel_desc*)(base + o_in), (const gsum_grad_param*)(base + o_in + dbytes), P, nugget,
                            (double*)(base + o_scr), dres, dgres);
         GS_CHECK(hipGetLastError());
         double* hres = (double*)((char*)ctx->hbatch + up(in_cap));
-        GS_CHECK(hipMemcpyAsync(hres, dres, (size_t)cnt * (258 + (size_t)P * 257) * 8, hipMemcpyDeviceToHost, s));
+        GS_CHECK(hipMemcpyAsync(hres, dres, (size_t)cnt * (GS_RES_LEN + (size_t)P * GS_GRES_LEN) * 8, hipMemcpyDeviceToHost, s));
         GS_CHECK(hipStreamSynchronize(s));
-        const double* hg = hres + (size_t)cnt * 258;
+        const double* hg = hres + (size_t)cnt * GS_RES_LEN;
         for (int e = 0; e < cnt; ++e) {
-            const double* r = hres + (size_t)e * 258;
-            const int i = lo + e;
-            for (int a = 0; a < k; ++a)
-                for (int b = 0; b < k; ++b) G_out[(size_t)i * k * k + a * k + b] = r[a * 16 + b];
-            sld_out[i] = r[256];
-            info_out[i] = (int64_t)r[257];
-            for (int p = 0; p < P; ++p) {
-                const double* g = hg + ((size_t)e * P + p) * 257;
-                const bool ok = info_out[i] == 0;              // not positive definite: no gradient pieces (the caller looks at info)
-                for (int a = 0; a < k; ++a)
-                    for (int b = 0; b < k; ++b) H_out[(((size_t)i * P + p) * k + a) * k + b] = ok ? g[a * 16 + b] : 0.0;
-                trace_out[(size_t)i * P + p] = ok ? g[256] : 0.0;
-            }
+            const size_t i = (size_t)(lo + e);
+            gs_unpack_value(hres + (size_t)e * GS_RES_LEN, k, i, G_out, sld_out, info_out);
+            for (int p = 0; p < P; ++p)
+                gs_unpack_grad(hg + ((size_t)e * P + p) * GS_GRES_LEN, info_out[i] == 0, k, P, i, p, H_out, trace_out);
         }
     }
     return 0;
@@ -404,11 +390,7 @@ static int gs_grad_batch_wave(gsum_ctx* ctx, const gsum_kernel_desc* descs, int 
         const int i = sl->pending;
         if (i < 0) return 0;
         GS_CHECK(hipStreamSynchronize(sl->sm));
-        for (int p = 0; p < P; ++p) {
-            for (int a = 0; a < k; ++a)
-                for (int b = 0; b < k; ++b) H_out[(((size_t)i * P + p) * k + a) * k + b] = sl->hgrad[(size_t)p * 257 + a * 16 + b];
-            trace_out[(size_t)i * P + p] = sl->hgrad[(size_t)p * 257 + 256];
-        }
+        for (int p = 0; p < P; ++p) gs_unpack_grad(sl->hgrad + (size_t)p * GS_GRES_LEN, true, k, P, (size_t)i, p, H_out, trace_out);
         sl->pending = -1;
         return 0;
     };
@@ -431,11 +413,8 @@ static int gs_grad_batch_wave(gsum_ctx* ctx, const gsum_kernel_desc* descs, int 
             for (int q = 0; q < g->cnt && !rc; ++q) {
                 const int i = off + g->first_eval + q;
                 if (i >= off + cnt) break;
-                if (info_out[i] != 0) {                       // not positive definite: no gradient pieces (the caller looks at info)
-                    for (int p = 0; p < P; ++p) {
-                        trace_out[(size_t)i * P + p] = 0.0;
-                        for (int ab = 0; ab < k * k; ++ab) H_out[((size_t)i * P + p) * k * k + ab] = 0.0;
-                    }
+                if (info_out[i] != 0) {                       // not positive definite: no gradient stage, zeros (gs_unpack_grad's rule)
+                    for (int p = 0; p < P; ++p) gs_unpack_grad(nullptr, false, k, P, (size_t)i, p, H_out, trace_out);
                     continue;
                 }
                 gs_slot* sl = &ctx->slots[slot++ % S];

@@ -149,7 +149,7 @@ static int gs_potrf_info(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
     if (gs_potrf(ctx, A)) return -1;
     if (gs_finalize(ctx, A)) return -1;
     GS_CHECK(hipStreamSynchronize(ctx->cur->sm));
-    *info = (int64_t)ctx->cur->hres[257];
+    *info = (int64_t)ctx->cur->hres[GS_RES_INFO];
     if (*info == GS_INFO_CHAIN_ABORT) {
         ctx->chain_persist = 0;
         ++ctx->chain_aborts;
@@ -213,8 +213,8 @@ int gsum_forward_gram(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, 
     if (gs_finalize(ctx, L)) return -1;
     GS_CHECK(hipStreamSynchronize(ctx->cur->sm));
     for (int i = 0; i < k; ++i)
-        for (int j = 0; j < k; ++j) G[i * k + j] = ctx->cur->hres[i * 16 + j];
-    *sum_log_diag = ctx->cur->hres[256];
+        for (int j = 0; j < k; ++j) G[i * k + j] = ctx->cur->hres[i * GS_RES_LD + j];
+    *sum_log_diag = ctx->cur->hres[GS_RES_SLD];
     return 0;
 }
 

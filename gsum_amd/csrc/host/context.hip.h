@@ -57,7 +57,7 @@ struct gs_slot {
     gsum_mat* ws = nullptr;          // workspace matrix of the fused path (reused across calls)
     int pending = -1;                // index of the evaluation in flight on this slot
     double* gws = nullptr; size_t gws_cap = 0;   // gradient path: this slot's U = L^-T, R^-1, V^T, per-parameter partials
-    double* hgrad = nullptr;                     // ... and its pinned read-back buffer (GSUM_MAX_GRAD x 257)
+    double* hgrad = nullptr;                     // ... and its pinned read-back buffer (GSUM_MAX_GRAD gradient records)
     gsum_kernel_desc last_desc;      // ... and what it was (a chain-schedule timeout re-runs it on the host-enqueued schedule)
     double last_nugget = 0.0;
     int last_index = 0;              // ... and its index in the call (its right-hand-side set)
@@ -198,7 +198,7 @@ struct gsum_ctx {
     const int32_t* set_of = nullptr;   // the current call's right-hand-side set per evaluation (host array; NULL: set 0 throughout)
     double* scratch = nullptr; size_t scratch_cap = 0;
     double* pscratch = nullptr; size_t pscratch_cap = 0;    // pivoted Cholesky: two trailing-matrix buffers, the panel, its bookkeeping
-    double* hbatch = nullptr; size_t hbatch_cap = 0;   // pinned host buffer for the fused paths' result blocks (258 doubles each)
+    double* hbatch = nullptr; size_t hbatch_cap = 0;   // pinned host buffer for the fused paths' result records
     double* gws = nullptr; size_t gws_cap = 0;     // gradient path: U = L^-T, R^-1, V^T, per-parameter partials
     double timers[4] = {0, 0, 0, 0};
     unsigned long long* dstamps = nullptr;   // 8 u64: phase stamps of the last diagonal-block kernel

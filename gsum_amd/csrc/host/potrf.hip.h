@@ -627,7 +627,7 @@ static int gs_finalize(gsum_ctx* ctx, gsum_mat* m) {
                        ctx->cur->dres);
     gs_prof_end(ctx, ctx->cur->sm, rec);
     GS_CHECK(hipGetLastError());
-    GS_CHECK(hipMemcpyAsync(ctx->cur->hres, ctx->cur->dres, 258 * sizeof(double), hipMemcpyDeviceToHost, ctx->cur->sm));
+    GS_CHECK(hipMemcpyAsync(ctx->cur->hres, ctx->cur->dres, GS_RES_LEN * sizeof(double), hipMemcpyDeviceToHost, ctx->cur->sm));
     return 0;
 }
 

@@ -42,7 +42,7 @@ static void gs_wave_release(gsum_ctx* ctx, bool streams) {
 static double gs_wave_ws_bytes(int64_t np) {
     const double T = (double)(np / GS_NB);
     return (double)(np + GS_BORDER) * (double)GS_LD(np) * 8.0 + T * GS_LTAB * 8.0 + (T / 2 + 1) * GS_LSIB * 8.0 +
-           (T + (double)np + 258.0) * 8.0 + 4.0;
+           (T + (double)np + (double)GS_RES_LEN) * 8.0 + 4.0;
 }
 
 // G groups in all, the first Gs of them with a chain stream of their own; group i >= Gs (a second cohort) runs on group (i - Gs)'s
@@ -90,7 +90,7 @@ static int gs_wave_prepare(gsum_ctx* ctx, int G, int B, int64_t n, int64_t np, i
         if (e == hipSuccess) e = hipMalloc((void**)&p.logdet, (size_t)B * T * sizeof(double));
         if (e == hipSuccess) e = hipMalloc((void**)&p.diag0, (size_t)B * np * sizeof(double));
         if (e == hipSuccess) e = hipMalloc((void**)&p.info, (size_t)B * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void**)&p.res, (size_t)B * 258 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&p.res, (size_t)B * GS_RES_LEN * sizeof(double));
         if (e != hipSuccess) {
             gs_wave_free_group(g);
             ctx->err = std::string("hipMalloc(group workspaces) failed: ") + hipGetErrorString(e);
@@ -194,7 +194,7 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
     size_t next_share = 0;
     if (gs_wave_prepare(ctx, G, B, n, np, std::min(Gs, G))) return -1;
     ctx->wave_last_streams = std::min(Gs, G) + 1;
-    if (gs_reserve_pinned(ctx, (size_t)n_kernels * 258 * sizeof(double))) return -1;
+    if (gs_reserve_pinned(ctx, (size_t)n_kernels * GS_RES_LEN * sizeof(double))) return -1;
     gs_wave* wv = &ctx->wave;
     // One plan per group: in a call's first round the groups' first macro-steps differ in length (option wave_head, decimal digits,
     // one per group) -- with every group four panels deep, the bulk stream's first update starts only after four chain steps (1.6 ms
@@ -366,7 +366,7 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
             hipLaunchKernelGGL(k_finalize_g, dim3((unsigned)g->cnt), dim3(256), 0, g->run, ca);
             gs_prof_end(ctx, g->run, rec);
             GS_CHECK(hipGetLastError());
-            GS_CHECK(hipMemcpyAsync(ctx->hbatch + (size_t)g->first_eval * 258, g->pool.res, (size_t)g->cnt * 258 * sizeof(double),
+            GS_CHECK(hipMemcpyAsync(ctx->hbatch + (size_t)g->first_eval * GS_RES_LEN, g->pool.res, (size_t)g->cnt * GS_RES_LEN * sizeof(double),
                                     hipMemcpyDeviceToHost, g->run));
             g->active = false;
             --live;
@@ -374,13 +374,7 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
     }
     for (int i = 0; i < G; ++i) GS_CHECK(hipStreamSynchronize(wv->g[i].run));
     GS_CHECK(hipStreamSynchronize(wv->sb));
-    for (int i = 0; i < n_kernels; ++i) {
-        const double* r = ctx->hbatch + (size_t)i * 258;
-        for (int a = 0; a < k; ++a)
-            for (int b = 0; b < k; ++b) G_out[(size_t)i * k * k + a * k + b] = r[a * 16 + b];
-        sld_out[i] = r[256];
-        info_out[i] = (int64_t)r[257];
-    }
+    for (int i = 0; i < n_kernels; ++i) gs_unpack_value(ctx->hbatch + (size_t)i * GS_RES_LEN, k, i, G_out, sld_out, info_out);
     return 0;
 }
 

@@ -248,7 +248,7 @@ struct gs_wv_pool {
     double* Ltab; double* Lsib;              // T x GS_LTAB, (T / 2 + 1) x GS_LSIB per workspace
     double* logdet; double* diag0;           // T, np per workspace
     int* info;                               // 1 per workspace
-    double* res;                             // 258 per workspace (k_finalize_g)
+    double* res;                             // one result record per workspace (k_finalize_g)
     int np, T;
 };
 struct gs_wv_chain_args {

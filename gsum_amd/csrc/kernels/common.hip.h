@@ -25,6 +25,19 @@ __device__ double gs_pivot_guard = 2.0 * 2.220446049250313e-16;
 #define GS_LSTR (GS_KC + 1)       // odd LDS row stride (17 doubles): the compiler pairs fragment reads into
                                   // ds_read2_b64, which banks mod 32 dwords -> rows 2 dwords apart, no conflicts
 
+// The result record of every fused evaluation path (k_finalize[_g], k_lml_small, k_lml_medium, k_grad_small), on the device and in the
+// pinned read-back buffers: G as GS_RES_LD x GS_RES_LD row-major (the corner of the bordered matrix, so its leading dimension is GS_BORDER
+// whatever the number k of right-hand sides; the host copies the leading k x k part out), then sum_i log L_ii, then info.
+// The gradient paths add P records per evaluation: H_p with the same leading dimension, then trace_p = tr(R^-1 dR_p).
+// Host side: gs_unpack_value / gs_unpack_grad (host/api_fused.hip.h) unpack whole records for the evaluation paths; gsum_forward_gram,
+// gs_potrf_info and the chain-abort test of gs_eval_harvest read single fields by these names.
+#define GS_RES_LD GS_BORDER
+#define GS_RES_SLD (GS_RES_LD * GS_RES_LD)        // index of sum_i log L_ii
+#define GS_RES_INFO (GS_RES_SLD + 1)              // index of info (a double: 0, the failing column, or GS_INFO_CHAIN_ABORT)
+#define GS_RES_LEN (GS_RES_INFO + 1)              // doubles per value record
+#define GS_GRES_TRACE (GS_RES_LD * GS_RES_LD)     // index of trace_p in a gradient record
+#define GS_GRES_LEN (GS_GRES_TRACE + 1)           // doubles per gradient record
+
 typedef double gs_d4 __attribute__((ext_vector_type(4)));
 typedef double gs_d2 __attribute__((ext_vector_type(2)));
 

@@ -6,7 +6,7 @@
 // ONE workgroup per evaluation builds K, factors it, solves for the right-hand sides and reduces the Gram
 // matrix; a launch evaluates a whole row of a likelihood grid.  Same arithmetic as the general path
 // (k_build's kernel functions, gs_diag_block), per-evaluation scratch in global memory (L2-resident).
-//   scratch per evaluation: A (128x128) | W^T (16x128, in a 128x128 slot);   res per evaluation: 258 doubles as k_finalize.
+//   scratch per evaluation: A (128x128) | W^T (16x128, in a 128x128 slot);   res per evaluation: one value record (layout: common.hip.h).
 // ------------------------------------------------------------------------------------------------
 #define GS_SMALL_SCRATCH (2 * 128 * 128)
 
@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, in
     const gsum_kernel_desc& desc = descs[blockIdx.x];      // in place (uniform address, read-only: scalar loads) -- a private copy is 712 B of scratch per lane
     double* A = scratch + (int64_t)blockIdx.x * GS_SMALL_SCRATCH;
     double* Wt = A + 128 * 128;                                         // W^T, 16 x 128 row-major (L2-resident)
-    double* out = res + (int64_t)blockIdx.x * 258;
+    double* out = res + (int64_t)blockIdx.x * GS_RES_LEN;
     if (zset) Z += (int64_t)zset[blockIdx.x] * n * k;                  // this evaluation's right-hand-side set (gsum_lml_resident_sets)
     // ---- kernel matrix (full symmetric 128x128 tile, identity padding beyond n)
     double* etab = us + 128 * GSUM_MAX_D;                               // exp tables th[16] | tl[16]
@@ -49,8 +49,8 @@ __global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, in
     const int bad = gs_diag_block<true, true>(A, 128, (double*)nullptr, (double*)nullptr, &ldet, dg0, nullptr, wsd, (n + 15) >> 4);
     if (bad) {
         if (t == 0) {
-            out[256] = 0.0;
-            out[257] = (double)bad;
+            out[GS_RES_SLD] = 0.0;
+            out[GS_RES_INFO] = (double)bad;
         }
         return;
     }
@@ -76,10 +76,10 @@ __global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, in
             }
         }
 #pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * 16 + fr] = g[x];
+        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
         if (lane == 0) {
-            out[256] = ldet;
-            out[257] = 0.0;
+            out[GS_RES_SLD] = ldet;
+            out[GS_RES_INFO] = 0.0;
         }
     }
 }
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
     double* diag0 = A + (int64_t)np * ld + (int64_t)T * 128 * 128;     // (the T x 128 x 128 slot before it held exported tables
                                                                        // while the right-hand sides had a sweep of their own)
     double* Wt = diag0 + np;                        // 16 x np, row-major
-    double* out = res + (int64_t)blockIdx.x * 258;
+    double* out = res + (int64_t)blockIdx.x * GS_RES_LEN;
     if (zset) Z += (int64_t)zset[blockIdx.x] * n * k;                  // this evaluation's right-hand-side set (gsum_lml_resident_sets)
     // diagnostics (option "diag_stamps"): shader cycles of workgroup 0 per phase -> stamps[40..47] =
     // {build, diagonal blocks, panel solves, sibling tiles, trailing tiles, W step, Gram + rest, total}
@@ -270,8 +270,8 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
                                           &ldet_blk, diag0 + c * 128, nullptr, lds);
             if (bad) {
                 if (t == 0) {
-                    out[256] = 0.0;
-                    out[257] = (double)(c * 128 + bad);
+                    out[GS_RES_SLD] = 0.0;
+                    out[GS_RES_INFO] = (double)(c * 128 + bad);
                 }
                 return;
             }
@@ -379,10 +379,10 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
             g = __builtin_amdgcn_mfma_f64_16x16x4f64(wv, wv, g, 0, 0, 0);
         }
 #pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * 16 + fr] = g[x];
+        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
         if (lane == 0) {
-            out[256] = ldet_sum;
-            out[257] = 0.0;
+            out[GS_RES_SLD] = ldet_sum;
+            out[GS_RES_INFO] = 0.0;
         }
     }
     phase(6);

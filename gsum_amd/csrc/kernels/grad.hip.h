@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_grad_trace(const double* Rinv, int64_t 
 }
 
 // H_p = V^T Q_p (16 x 16) and sum_i trow_p[i], in two deterministic stages.  Stage 1 (grid: chunks x P): chunk c
-// reduces rows [c * rows_per, (c + 1) * rows_per) into part[(p * chunks + c) * 257 ...]; stage 2 (grid: P) adds the
+// reduces rows [c * rows_per, (c + 1) * rows_per) into gradient record p * chunks + c of part (layout: common.hip.h); stage 2 (grid: P) adds the
 // chunks in index order.
 __global__ __launch_bounds__(256) void k_grad_reduce1(const double* Vt, int64_t ldv, const double* Q, const double* trow, int n,
                                                        int rows_per, double* part) {
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce1(const double* Vt, int64_t 
     const double* Qp = Q + (int64_t)p * n * 16;
     double h = 0.0;
     for (int i = lo; i < hi; ++i) h = __builtin_fma(Vt[(int64_t)a * ldv + i], Qp[(int64_t)i * 16 + b], h);
-    double* o = part + ((int64_t)p * gridDim.x + c) * 257;
+    double* o = part + ((int64_t)p * gridDim.x + c) * GS_GRES_LEN;
     o[t] = h;
     double ts = 0.0;
     for (int i = lo + t; i < hi; i += 256) ts += trow[(int64_t)p * n + i];
@@ -166,19 +166,19 @@ __global__ __launch_bounds__(256) void k_grad_reduce1(const double* Vt, int64_t 
         if (t < w) red[t] += red[t + w];
         __syncthreads();
     }
-    if (t == 0) o[256] = red[0];
+    if (t == 0) o[GS_GRES_TRACE] = red[0];
 }
 
 __global__ __launch_bounds__(256) void k_grad_reduce2(const double* part, int chunks, double* out) {
     const int t = threadIdx.x, p = blockIdx.x;
-    const double* src = part + (int64_t)p * chunks * 257;
+    const double* src = part + (int64_t)p * chunks * GS_GRES_LEN;
     double h = 0.0;
-    for (int c = 0; c < chunks; ++c) h += src[(int64_t)c * 257 + t];
-    out[(int64_t)p * 257 + t] = h;
+    for (int c = 0; c < chunks; ++c) h += src[(int64_t)c * GS_GRES_LEN + t];
+    out[(int64_t)p * GS_GRES_LEN + t] = h;
     if (t == 0) {
         double ts = 0.0;
-        for (int c = 0; c < chunks; ++c) ts += src[(int64_t)c * 257 + 256];
-        out[(int64_t)p * 257 + 256] = ts;
+        for (int c = 0; c < chunks; ++c) ts += src[(int64_t)c * GS_GRES_LEN + GS_GRES_TRACE];
+        out[(int64_t)p * GS_GRES_LEN + GS_GRES_TRACE] = ts;
     }
 }
 
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce2(const double* part, int ch
 //   gs_diag_block, R^-1 = L^-T L^-1 and V^T = W^T L^-1 on the matrix cores (gs_tile128), then per hyperparameter dR_p entry by entry
 //   (k_grad_contract's formulas), trace_p = tr(R^-1 dR_p) on the way, Q_p = dR_p V on the matrix cores, H_p = V^T Q_p.
 //   scratch per evaluation: A | W^T (16 rows) and V^T (16 rows) in one slot | L^-1 | L^-T | R^-1  (five 128 x 128 slots);
-//   res: 258 doubles as k_finalize;  gres: P x 257 (H_p 16 x 16, then the trace).
+//   res: one value record;  gres: P gradient records (layouts: common.hip.h).
 // ------------------------------------------------------------------------------------------------
 #define GS_GSMALL_SCRATCH (5 * 128 * 128)
 template <bool TREE>
@@ -213,9 +213,10 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
     double* Linv = A + 2 * 128 * 128;
     double* Ut = A + 3 * 128 * 128;                                     // L^-T, row-major
     double* Rinv = A + 4 * 128 * 128;
-    double* out = res + (int64_t)blockIdx.x * 258;
-    double* gout = gres + (int64_t)blockIdx.x * P * 257;
-    // ---- kernel matrix, factorisation, W^T, Gram matrix: k_lml_small, statement for statement
+    double* out = res + (int64_t)blockIdx.x * GS_RES_LEN;
+    double* gout = gres + (int64_t)blockIdx.x * P * GS_GRES_LEN;
+    // ---- kernel matrix, factorisation, W^T, Gram matrix: k_lml_small, statement for statement (a pasted copy on purpose, see DESIGN.md section 9:
+    // a shared body changes both kernels' instruction order and waits for a measurement of the small paths)
     double* etab = us + 128 * GSUM_MAX_D;
     if (t < 16) etab[t] = gs_exp_th[t];
     else if (t < 32) etab[t] = gs_exp_tl[t - 16];
@@ -232,8 +233,8 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
     const int bad = gs_diag_block<true, true>(A, 128, Linv, (double*)nullptr, &ldet, dg0, nullptr, wsd, (n + 15) >> 4);
     if (bad) {
         if (t == 0) {
-            out[256] = 0.0;
-            out[257] = (double)bad;
+            out[GS_RES_SLD] = 0.0;
+            out[GS_RES_INFO] = (double)bad;
         }
         return;
     }
@@ -257,10 +258,10 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
             }
         }
 #pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * 16 + fr] = g[x];
+        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
         if (lane == 0) {
-            out[256] = ldet;
-            out[257] = 0.0;
+            out[GS_RES_SLD] = ldet;
+            out[GS_RES_INFO] = 0.0;
         }
     }
     // ---- L^-T (the transpose of the block inverse), then on the matrix cores V^T = W^T L^-1 = W^T (L^-T)^T and R^-1 = L^-T (L^-T)^T
@@ -331,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
         if (t == 0) {                                                  // the trace: 256 partial sums in index order (deterministic)
             double ts = 0.0;
             for (int q = 0; q < 256; ++q) ts += red[q];
-            gout[(int64_t)p * 257 + 256] = ts;
+            gout[(int64_t)p * GS_GRES_LEN + GS_GRES_TRACE] = ts;
         }
         gs_tile128(Qg, 16, dRm, 128, Vt, 128, n16, 16, n16, 0, 1.0, wsd);          // Q_p[i][c] = sum_j dR_p[i][j] V^T[c][j]
         {
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
             const int a2 = t >> 4, b2 = t & 15;                        // H_p = V^T Q_p, rows in index order
             double h = 0.0;
             for (int i = 0; i < n; ++i) h = __builtin_fma(vs[a2 * 128 + i], qs[i * 16 + b2], h);
-            gout[(int64_t)p * 257 + t] = h;
+            gout[(int64_t)p * GS_GRES_LEN + t] = h;
         }
         __syncthreads();
     }

@@ -540,7 +540,7 @@ __global__ __launch_bounds__(512, 7) void k_gemm_ld3g(const gs_wv_gemm_args a) {
 __global__ __launch_bounds__(512, 7) void k_gemm_ld3n(const gs_wv_gemm_args a) { gs_gemm_ld3g_body(a); }
 
 // Read-out of the bordered factorisation: G = -(corner), sum of the per-block log-det partials.
-// res[0..255] = G (16x16 row-major), res[256] = sum_i log L_ii, res[257] = info.
+// Writes the result record (layout: kernels/common.hip.h), one thread per entry of G.
 __global__ __launch_bounds__(256) void k_finalize(const double* A, int64_t ld, int np, const double* logdet,
                                                    int T, const int* info, double* res) {
     const int t = threadIdx.x;
@@ -549,8 +549,8 @@ __global__ __launch_bounds__(256) void k_finalize(const double* A, int64_t ld, i
     if (t == 0) {
         double s = 0.0;
         for (int i = 0; i < T; ++i) s += logdet[i];
-        res[256] = s;
-        res[257] = (double)(*info);
+        res[GS_RES_SLD] = s;
+        res[GS_RES_INFO] = (double)(*info);
     }
 }
 
@@ -560,13 +560,13 @@ __global__ __launch_bounds__(256) void k_finalize_g(const gs_wv_chain_args a) {
     const int t = threadIdx.x;
     const int r = t >> 4, c = t & 15;
     const double* A = a.p.A + q * a.p.strideA;
-    double* res = a.p.res + q * 258;
+    double* res = a.p.res + q * GS_RES_LEN;
     res[t] = -A[(int64_t)(a.p.np + r) * a.p.ld + a.p.np + c];
     if (t == 0) {
         double s = 0.0;
         for (int i = 0; i < a.p.T; ++i) s += a.p.logdet[q * a.p.T + i];
-        res[256] = s;
-        res[257] = (double)a.p.info[q];
+        res[GS_RES_SLD] = s;
+        res[GS_RES_INFO] = (double)a.p.info[q];
     }
 }
 
