@@ -10,29 +10,54 @@
 // ------------------------------------------------------------------------------------------------
 #define GS_SMALL_SCRATCH (2 * 128 * 128)
 
-// TREE: the instantiation the host launches when a call carries a Sum / Product tree (n_ops > 0): such an evaluation builds its matrix
-// with gs_build_tile128_tree, every other evaluation of the call with the flattened code; a call of flattened descriptors only runs the
-// TREE = false kernel, whose register budget the postfix walk never touches.
-template <bool TREE>
-__global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, int d, const double* Z, int k,
-                                                    const gsum_kernel_desc* __restrict__ descs, double nugget, double* scratch,
-                                                    double* res, const int32_t* zset) {
-#pragma clang fp contract(off)
-    __shared__ double dg0[128];
-    __shared__ double ldet;
-    __shared__ __attribute__((aligned(16))) double wsd[GS_DIAG_WS];     // lent to the build (us) and the solve (Wt) too:
-    double* us = wsd;                                                   // 78.6 KB of LDS in all, two evaluations per CU
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const gsum_kernel_desc& desc = descs[blockIdx.x];      // in place (uniform address, read-only: scalar loads) -- a private copy is 712 B of scratch per lane
-    double* A = scratch + (int64_t)blockIdx.x * GS_SMALL_SCRATCH;
-    double* Wt = A + 128 * 128;                                         // W^T, 16 x 128 row-major (L2-resident)
-    double* out = res + (int64_t)blockIdx.x * GS_RES_LEN;
-    if (zset) Z += (int64_t)zset[blockIdx.x] * n * k;                  // this evaluation's right-hand-side set (gsum_lml_resident_sets)
-    // ---- kernel matrix (full symmetric 128x128 tile, identity padding beyond n)
-    double* etab = us + 128 * GSUM_MAX_D;                               // exp tables th[16] | tl[16]
+// The two exp tables th[16] | tl[16] into LDS, by threads 0 .. 31 (first read behind the caller's next barrier).
+__device__ __forceinline__ void gs_stage_exp_tables(double* etab, int t) {
     if (t < 16) etab[t] = gs_exp_th[t];
     else if (t < 32) etab[t] = gs_exp_tl[t - 16];
+}
+
+// The value record of a member that is not positive definite (thread 0): info = 1-based index of the failing pivot.
+__device__ __forceinline__ void gs_record_failed(double* out, int info, int t) {
+    if (t == 0) {
+        out[GS_RES_SLD] = 0.0;
+        out[GS_RES_INFO] = (double)info;
+    }
+}
+
+// The value record of a member that is positive definite, by one wave: G = W^T W (16 x 16; W^T is 16 x np, row-major with leading
+// dimension ldw; np / 4 MFMA steps in ascending k), sum log diag, info = 0.
+__device__ __forceinline__ void gs_record_gram(double* out, const double* Wt, int64_t ldw, int np, const double* sld, int lane) {
+    const int fr = lane & 15, fq = lane >> 4;
+    gs_d4 g = {0.0, 0.0, 0.0, 0.0};
+    for (int s4 = 0; s4 < np / 4; ++s4) {
+        const double wv = Wt[fr * ldw + 4 * s4 + fq];
+        g = __builtin_amdgcn_mfma_f64_16x16x4f64(wv, wv, g, 0, 0, 0);
+    }
+#pragma unroll
+    for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
+    if (lane == 0) {
+        out[GS_RES_SLD] = *sld;
+        out[GS_RES_INFO] = 0.0;
+    }
+}
+
+// The value steps of the one-workgroup kernels (k_lml_small, k_grad_small): kernel matrix, factorisation, W^T, Gram matrix, value record.
+// A, Wt: the evaluation's 128 x 128 and 16 x 128 slots; Linv: where the explicit block inverse goes, or null; dg0[128], ldet, wsd[GS_DIAG_WS]:
+// the caller's LDS (wsd is lent to the build and the solve too and holds the block's substitution tables on return).  Returns
+// gs_diag_block's `bad`: non-zero = not positive definite, the failed record is written and the caller returns.
+// TREE: the instantiation the host launches when a call carries a Sum / Product tree (n_ops > 0): such an evaluation builds its matrix
+// with gs_build_tile128_tree, every other evaluation of the call with the flattened code; a call of flattened descriptors only runs the
+// TREE = false kernels, whose register budget the postfix walk never touches.
+template <bool TREE>
+__device__ __forceinline__ int gs_small_value(const double* X, int n, int d, const double* Z, int k, const gsum_kernel_desc& desc, double nugget,
+                                              double* A, double* Wt, double* Linv, double* out, double* dg0, double* ldet, double* wsd) {
+#pragma clang fp contract(off)
+    double* us = wsd;
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    // ---- kernel matrix (full symmetric 128x128 tile, identity padding beyond n)
+    double* etab = us + 128 * GSUM_MAX_D;                               // exp tables th[16] | tl[16]
+    gs_stage_exp_tables(etab, t);
     for (int idx = t; idx < 128 * d; idx += 256) {
         const int r = idx / d, dd = idx - r * d;
         const double ls = desc.anisotropic ? desc.length_scale[dd] : desc.length_scale[0];
@@ -40,19 +65,16 @@ __global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, in
     }
     __syncthreads();
     // (the one tile is a diagonal tile: rows and columns are the same points; family / dimension as template parameters)
-    if (TREE && descs[blockIdx.x].n_ops > 0) gs_build_tile128_tree(A, 128, X, 0, 0, n, d, descs[blockIdx.x], nugget, dg0, w, lane);
+    if (TREE && desc.n_ops > 0) gs_build_tile128_tree(A, 128, X, 0, 0, n, d, desc, nugget, dg0, w, lane);
     else gs_build_tile128_any(A, 128, us, us, etab, etab + 16, 0, 0, n, d, desc, nugget, dg0, w, lane);
     __threadfence_block();
     __syncthreads();
     // ---- Cholesky of the block; its substitution tables stay in wsd
     // (only the micro-blocks that hold points are factorised: the rest of the block is identity padding, gs_d2_wave<.., PARTIAL>)
-    const int bad = gs_diag_block<true, true>(A, 128, (double*)nullptr, (double*)nullptr, &ldet, dg0, nullptr, wsd, (n + 15) >> 4);
+    const int bad = gs_diag_block<true, true>(A, 128, Linv, (double*)nullptr, ldet, dg0, nullptr, wsd, (n + 15) >> 4);
     if (bad) {
-        if (t == 0) {
-            out[GS_RES_SLD] = 0.0;
-            out[GS_RES_INFO] = (double)bad;
-        }
-        return;
+        gs_record_failed(out, bad, t);
+        return bad;
     }
     // ---- W^T = Z^T L^-T: the right-hand sides as 16 rows of 128 points, solved by one wave against the tables
     for (int idx = t; idx < 16 * 128; idx += 256) {
@@ -64,24 +86,24 @@ __global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, in
     if (w == 0) gs_panel16(Wt, 128, 16, wsd, lane);
     __threadfence_block();
     __syncthreads();
-    const int fr = lane & 15, fq = lane >> 4;
     // ---- Gram matrix G = W^T W (16 x 16, K = 128) by wave 0
-    if (w == 0) {
-        gs_d4 g = {0.0, 0.0, 0.0, 0.0};
-        for (int kb = 0; kb < 8; ++kb) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const double wv = Wt[fr * 128 + 16 * kb + 4 * s4 + fq];
-                g = __builtin_amdgcn_mfma_f64_16x16x4f64(wv, wv, g, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
-        if (lane == 0) {
-            out[GS_RES_SLD] = ldet;
-            out[GS_RES_INFO] = 0.0;
-        }
-    }
+    if (w == 0) gs_record_gram(out, Wt, 128, 128, ldet, lane);
+    return 0;
+}
+
+template <bool TREE>
+__global__ __launch_bounds__(256, 2) void k_lml_small(const double* X, int n, int d, const double* Z, int k,
+                                                    const gsum_kernel_desc* __restrict__ descs, double nugget, double* scratch,
+                                                    double* res, const int32_t* zset) {
+    __shared__ double dg0[128];
+    __shared__ double ldet;
+    __shared__ __attribute__((aligned(16))) double wsd[GS_DIAG_WS];     // lent to the build (us) and the solve (Wt) too:
+                                                                        // 78.6 KB of LDS in all, two evaluations per CU
+    const gsum_kernel_desc& desc = descs[blockIdx.x];      // in place (uniform address, read-only: scalar loads) -- a private copy is 712 B of scratch per lane
+    double* A = scratch + (int64_t)blockIdx.x * GS_SMALL_SCRATCH;
+    double* Wt = A + 128 * 128;                                         // W^T, 16 x 128 row-major (L2-resident)
+    if (zset) Z += (int64_t)zset[blockIdx.x] * n * k;                  // this evaluation's right-hand-side set (gsum_lml_resident_sets)
+    (void)gs_small_value<TREE>(X, n, d, Z, k, desc, nugget, A, Wt, nullptr, res + (int64_t)blockIdx.x * GS_RES_LEN, dg0, &ldet, wsd);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -235,8 +257,7 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
         double* ui = lds;
         double* uj = lds + 128 * GSUM_MAX_D;
         double* etab = lds + 2 * 128 * GSUM_MAX_D;      // exp tables th[16] | tl[16] (first read behind the loop's barriers)
-        if (t < 16) etab[t] = gs_exp_th[t];
-        else if (t < 32) etab[t] = gs_exp_tl[t - 16];
+        gs_stage_exp_tables(etab, t);
         for (int bi = 0; bi < T; ++bi)
             for (int bj = 0; bj <= bi; ++bj) {
                 __syncthreads();
@@ -269,10 +290,7 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
             const int bad = gs_diag_block(A + (int64_t)c * 128 * ld + c * 128, ld, (double*)nullptr, (double*)nullptr,
                                           &ldet_blk, diag0 + c * 128, nullptr, lds);
             if (bad) {
-                if (t == 0) {
-                    out[GS_RES_SLD] = 0.0;
-                    out[GS_RES_INFO] = (double)(c * 128 + bad);
-                }
+                gs_record_failed(out, c * 128 + bad, t);
                 return;
             }
             if (t == 0) ldet_sum += ldet_blk;
@@ -372,19 +390,7 @@ __global__ __launch_bounds__(256, 2) void k_lml_medium(const double* X, int n, i
     __threadfence_block();
     __syncthreads();                               // W^T complete (its last block was solved by whichever wave had the group)
     // ---- Gram matrix G = W^T W by wave 0 (ascending k), log-det, info
-    if (w == 0) {
-        gs_d4 g = {0.0, 0.0, 0.0, 0.0};
-        for (int s4 = 0; s4 < np / 4; ++s4) {
-            const double wv = Wt[(int64_t)fr * np + 4 * s4 + fq];
-            g = __builtin_amdgcn_mfma_f64_16x16x4f64(wv, wv, g, 0, 0, 0);
-        }
-#pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
-        if (lane == 0) {
-            out[GS_RES_SLD] = ldet_sum;
-            out[GS_RES_INFO] = 0.0;
-        }
-    }
+    if (w == 0) gs_record_gram(out, Wt, np, np, &ldet_sum, lane);
     phase(6);
     if (stamping) {
         for (int i = 0; i < 7; ++i) stamps[40 + i] = ph[i];

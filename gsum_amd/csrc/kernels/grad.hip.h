@@ -187,8 +187,8 @@ __global__ __launch_bounds__(256) void k_grad_reduce2(const double* part, int ch
 // Value + gradient pieces for n <= 128 in ONE workgroup per evaluation (round 5): the reference's own problem sizes are 5-100 points
 // and its fit() drives L-BFGS with log_marginal_likelihood(theta, eval_gradient=True) (models.py:634-640, 957-958, 1041-1056) -- the
 // general path's dozen launches and two synchronisations cost 250 us per objective evaluation there, this kernel ~60.
-//   k_lml_small's steps (same code: G, sum log diag and info equal the value path's bit for bit), the explicit block inverse from
-//   gs_diag_block, R^-1 = L^-T L^-1 and V^T = W^T L^-1 on the matrix cores (gs_tile128), then per hyperparameter dR_p entry by entry
+//   k_lml_small's steps (the same code, gs_small_value: G, sum log diag and info equal the value path's bit for bit) with the explicit block
+//   inverse from gs_diag_block, R^-1 = L^-T L^-1 and V^T = W^T L^-1 on the matrix cores (gs_tile128), then per hyperparameter dR_p entry by entry
 //   (k_grad_contract's formulas), trace_p = tr(R^-1 dR_p) on the way, Q_p = dR_p V on the matrix cores, H_p = V^T Q_p.
 //   scratch per evaluation: A | W^T (16 rows) and V^T (16 rows) in one slot | L^-1 | L^-T | R^-1  (five 128 x 128 slots);
 //   res: one value record;  gres: P gradient records (layouts: common.hip.h).
@@ -203,9 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
     __shared__ double ldet;
     __shared__ __attribute__((aligned(16))) double wsd[GS_DIAG_WS];     // the build's points, the block's tables, the tile's stages, the contractions' rows
     static_assert(GS_DIAG_WS >= GS_TILE_LD_DOUBLES, "one LDS workspace serves every phase");
-    double* us = wsd;
-    const int t = threadIdx.x, lane = t & 63;
-    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int t = threadIdx.x;
     const gsum_kernel_desc& desc = descs[blockIdx.x];
     double* A = scratch + (int64_t)blockIdx.x * GS_GSMALL_SCRATCH;
     double* Wt = A + 128 * 128;                                         // W^T: 16 x 128
@@ -213,57 +211,9 @@ __global__ __launch_bounds__(256, 2) void k_grad_small(const double* X, int n, i
     double* Linv = A + 2 * 128 * 128;
     double* Ut = A + 3 * 128 * 128;                                     // L^-T, row-major
     double* Rinv = A + 4 * 128 * 128;
-    double* out = res + (int64_t)blockIdx.x * GS_RES_LEN;
     double* gout = gres + (int64_t)blockIdx.x * P * GS_GRES_LEN;
-    // ---- kernel matrix, factorisation, W^T, Gram matrix: k_lml_small, statement for statement (a pasted copy on purpose, see DESIGN.md section 9:
-    // a shared body changes both kernels' instruction order and waits for a measurement of the small paths)
-    double* etab = us + 128 * GSUM_MAX_D;
-    if (t < 16) etab[t] = gs_exp_th[t];
-    else if (t < 32) etab[t] = gs_exp_tl[t - 16];
-    for (int idx = t; idx < 128 * d; idx += 256) {
-        const int r = idx / d, dd = idx - r * d;
-        const double ls = desc.anisotropic ? desc.length_scale[dd] : desc.length_scale[0];
-        us[idx] = r < n ? X[(int64_t)r * d + dd] / ls : 0.0;
-    }
-    __syncthreads();
-    if (TREE && descs[blockIdx.x].n_ops > 0) gs_build_tile128_tree(A, 128, X, 0, 0, n, d, descs[blockIdx.x], nugget, dg0, w, lane);
-    else gs_build_tile128_any(A, 128, us, us, etab, etab + 16, 0, 0, n, d, desc, nugget, dg0, w, lane);
-    __threadfence_block();
-    __syncthreads();
-    const int bad = gs_diag_block<true, true>(A, 128, Linv, (double*)nullptr, &ldet, dg0, nullptr, wsd, (n + 15) >> 4);
-    if (bad) {
-        if (t == 0) {
-            out[GS_RES_SLD] = 0.0;
-            out[GS_RES_INFO] = (double)bad;
-        }
-        return;
-    }
-    for (int idx = t; idx < 16 * 128; idx += 256) {
-        const int c = idx >> 7, i = idx & 127;
-        Wt[idx] = (c < k && i < n) ? Z[(int64_t)i * k + c] : 0.0;
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (w == 0) gs_panel16(Wt, 128, 16, wsd, lane);
-    __threadfence_block();
-    __syncthreads();
-    const int fr = lane & 15, fq = lane >> 4;
-    if (w == 0) {
-        gs_d4 g = {0.0, 0.0, 0.0, 0.0};
-        for (int kb = 0; kb < 8; ++kb) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const double wv = Wt[fr * 128 + 16 * kb + 4 * s4 + fq];
-                g = __builtin_amdgcn_mfma_f64_16x16x4f64(wv, wv, g, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int x = 0; x < 4; ++x) out[(fq + 4 * x) * GS_RES_LD + fr] = g[x];
-        if (lane == 0) {
-            out[GS_RES_SLD] = ldet;
-            out[GS_RES_INFO] = 0.0;
-        }
-    }
+    // ---- kernel matrix, factorisation (with the explicit block inverse), W^T, Gram matrix, value record: gs_small_value (fused.hip.h)
+    if (gs_small_value<TREE>(X, n, d, Z, k, desc, nugget, A, Wt, Linv, res + (int64_t)blockIdx.x * GS_RES_LEN, dg0, &ldet, wsd)) return;
     // ---- L^-T (the transpose of the block inverse), then on the matrix cores V^T = W^T L^-1 = W^T (L^-T)^T and R^-1 = L^-T (L^-T)^T
     // (beyond n the factor is the identity: everything below works on the leading n16 x n16 part, n16 = n rounded up to the tiles' K step)
     const int n16 = (n + 15) & ~15;
