@@ -880,9 +880,12 @@ def main():
     with open(os.path.join(HERE, "s5_predict.json"), "w") as f:      # ~10 minutes on 8 cores, ~15 GB
         json.dump(gen_s5_predict(), f, indent=1)
     import sklearn, scipy
+    with open(os.path.join(HERE, "VERSIONS.json")) as f:             # other makers keep lines of their own here
+        versions = json.load(f)
+    versions.update(numpy=np.__version__, scipy=scipy.__version__, sklearn=sklearn.__version__,
+                    reference="buqeye/gsum v0.3 @ /root/reference")
     with open(os.path.join(HERE, "VERSIONS.json"), "w") as f:
-        json.dump(dict(numpy=np.__version__, scipy=scipy.__version__, sklearn=sklearn.__version__,
-                       reference="buqeye/gsum v0.3 @ /root/reference"), f, indent=1)
+        json.dump(versions, f, indent=1)
 
 
 if __name__ == "__main__":
