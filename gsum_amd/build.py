@@ -12,6 +12,8 @@
                         interval coverage.  Its own small library, built like the variogram's.
 ``libgsum_pointwise.so`` the grid log likelihood and the interval coverage of TruncationPointwise (include/gsum_pointwise.h).  Its own
                         small library, built like the variogram's.
+``libgsum_loo.so``      the leave-one-out diagnostics (include/gsum_loo.h): the inverse of a Cholesky factor, the diagonal of the
+                        precision matrix and (L L^T)^-1 R.  Its own small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations
@@ -38,7 +40,7 @@ SIDE_SCAFFOLD = os.path.join(HERE, "csrc", "host", "sidelib.hip.h")      # the h
 SIDE = {name: (os.path.join(HERE, "csrc", f"gsum_{name}.hip"), os.path.join(HERE, "csrc", f"gsum_{name}.map"),
                os.path.join(HERE, "csrc", "kernels", f"{kernels}.hip.h"), os.path.join(ROOT, "include", f"gsum_{name}.h"),
                os.path.join(HERE, f"libgsum_{name}.so"))
-        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"))}
+        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"), ("loo", "loo"))}
 
 
 def hipcc_path():
@@ -74,6 +76,10 @@ def build_refdist(force: bool = False, verbose: bool = False) -> str:
 
 def build_pointwise(force: bool = False, verbose: bool = False) -> str:
     return build_side("pointwise", force, verbose)
+
+
+def build_loo(force: bool = False, verbose: bool = False) -> str:
+    return build_side("loo", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:

@@ -821,6 +821,20 @@ class ConjugateGaussianProcess:
         center = self.center_ if self._fit else self.center0
         return self.basis(X) @ center
 
+    def loo(self, y=None):
+        """The plug-in leave-one-out predictions of the fitted process at its training points (``LooResult``; loo.py): mean =
+        ``center_``, cov = ``cov_factor_`` (R + nugget I), whose factor is sqrt(``cov_factor_``) times the one ``fit`` holds.  ``y``,
+        (n,) or (n, n_curves), defaults to the training curves."""
+        if isinstance(self, ConjugateStudentProcess):
+            raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out is not provided")
+        if not self._fit or self._L_dev is None:
+            raise ValueError("loo needs a fitted process: call fit first")
+        from .loo import loo_from_factor
+        L = np.sqrt(float(np.squeeze(self.cov_factor_))) * self._L_dev.to_host()
+        X = np.asarray(self.X_train_, dtype=float)
+        y = self.y_train_ if y is None else y
+        return loo_from_factor(L, y, mean=self.mean(X), device=self.device, backend=self.backend)
+
     def _cov_parts(self, d):
         """(factor, descriptor): the process covariance is ``factor * kernel_desc(X[, Xp])`` -- prior quantities before ``fit``
         (models.py:579-589), ``cov_factor_`` and the fitted kernel after (:590-599).  One-argument form: the descriptor's own white

@@ -96,11 +96,14 @@ class Diagnostic:
         self._ctx, self.backend = _context(device, backend)
         cov = np.asarray(cov, dtype=float)
         self._mean = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, dtype=float), (cov.shape[0],)))
-        self._L = self._P = None
+        self._L = self._P = self._loo = None
         self._L = _factor(self._ctx, cov, pivot=False)
         self._P = _factor(self._ctx, cov, pivot=True)
 
     def close(self):
+        if getattr(self, "_loo", None) is not None:
+            self._loo.free()
+            self._loo = None
         for name in ("_L", "_P"):
             M = getattr(self, name, None)
             if M is not None:
@@ -158,6 +161,22 @@ class Diagnostic:
             w, V = np.linalg.eigh(self.cov)
             self._eig = V[:, ::-1] @ np.diag(np.sqrt(w[::-1]))
         return np.linalg.solve(self._eig, (np.asarray(y, dtype=float).T - self.mean).T)
+
+    def loo(self, y):
+        R"""The leave-one-out predictions of y, (n_samples, [n_curves]): each point against all the others (``LooResult``; loo.py).
+        The resident factor goes to the host and into the leave-one-out library once; its inverse stays there until ``close()``."""
+        if self.df is not None:
+            raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out (df set) is not provided")
+        if self._L is None:
+            raise ValueError("Diagnostic is closed")
+        if self._loo is None:
+            from .loo import LooFactor
+            self._loo = LooFactor(self._L.to_host(), device=self._ctx.device, backend=self.backend)
+        return self._loo.loo(y, self._mean)
+
+    def loo_errors(self, y):
+        R"""The standardised leave-one-out errors a_i / sqrt(p_i), shape (n_samples, [n_curves])."""
+        return self.loo(y).error
 
     def chi2(self, y):
         return np.sum(self.individual_errors(y), axis=0)
