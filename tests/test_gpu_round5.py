@@ -345,11 +345,12 @@ def test_truncation_std_moves_no_square_matrix(monkeypatch):
     np.testing.assert_allclose(sd, np.sqrt(np.diag(cg.cov(Xs))), rtol=1e-13)
 
 
-@pytest.mark.parametrize("n,m", [(700, 300), (2304, 1100), (2200, 1300)])
+@pytest.mark.parametrize("n,m", [(700, 300), (2304, 1100), (2200, 1300), (1100, 1061)])
 def test_predict_sweep_on_panel256_equals_the_three_launch_sweep(n, m):
     """The predictive sweep V^T = K* L^-T with every pair of block columns solved by ONE k_panel256 launch (sibling images rebuilt from
     the factor: k_make_lsib) against the k_panel / K = 128 GEMM / k_panel sweep of rounds 1-4: same arithmetic, same bits --
-    column sums of squares, V^T W and the full V^T V (models.py:822-836)."""
+    column sums of squares, V^T W and the full V^T V (models.py:822-836).  (1100, 1061): nine block columns without the chain schedule --
+    the look-ahead sweep then ends on a single block (gs_trsm_rows instead of gs_panel256) and leaves its loop through cn >= np."""
     lab = gsum_amd.lab_context(0)
     rng = np.random.RandomState(n)
     X = rng.rand(n, 2) * np.array([0.35, 0.65]) * np.sqrt(n)
