@@ -12,8 +12,9 @@
                         interval coverage.  Its own small library, built like the variogram's.
 ``libgsum_pointwise.so`` the grid log likelihood and the interval coverage of TruncationPointwise (include/gsum_pointwise.h).  Its own
                         small library, built like the variogram's.
-``libgsum_loo.so``      the leave-one-out diagnostics (include/gsum_loo.h): the inverse of a Cholesky factor, the diagonal of the
-                        precision matrix and (L L^T)^-1 R.  Its own small library, built like the variogram's.
+``libgsum_loo.so``      the leave-one-out and leave-group-out diagnostics (include/gsum_loo.h): the inverse of a Cholesky factor, the
+                        diagonal and the blocks of the precision matrix, (L L^T)^-1 R and the predictions of every group of a
+                        partition from the points outside it.  Its own small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations

@@ -827,13 +827,26 @@ class ConjugateGaussianProcess:
         (n,) or (n, n_curves), defaults to the training curves."""
         if isinstance(self, ConjugateStudentProcess):
             raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out is not provided")
-        if not self._fit or self._L_dev is None:
-            raise ValueError("loo needs a fitted process: call fit first")
         from .loo import loo_from_factor
+        L, y, mean = self._plug_in(y, "loo")
+        return loo_from_factor(L, y, mean=mean, device=self.device, backend=self.backend)
+
+    def _plug_in(self, y, who):
+        """(factor, curves, mean) of the plug-in Gaussian at the training points."""
+        if not self._fit or self._L_dev is None:
+            raise ValueError(f"{who} needs a fitted process: call fit first")
         L = np.sqrt(float(np.squeeze(self.cov_factor_))) * self._L_dev.to_host()
         X = np.asarray(self.X_train_, dtype=float)
-        y = self.y_train_ if y is None else y
-        return loo_from_factor(L, y, mean=self.mean(X), device=self.device, backend=self.backend)
+        return L, (self.y_train_ if y is None else y), self.mean(X)
+
+    def kfold(self, folds, y=None):
+        """The plug-in leave-group-out predictions of the fitted process at its training points (``FoldResult``; ``folds`` as in
+        ``LooFactor.folds``), with the mean and covariance of ``loo``."""
+        if isinstance(self, ConjugateStudentProcess):
+            raise NotImplementedError("kfold is the Gaussian leave-group-out; a Student-t one is not provided")
+        from .loo import kfold_from_factor
+        L, y, mean = self._plug_in(y, "kfold")
+        return kfold_from_factor(L, y, folds, mean=mean, device=self.device, backend=self.backend)
 
     def _cov_parts(self, d):
         """(factor, descriptor): the process covariance is ``factor * kernel_desc(X[, Xp])`` -- prior quantities before ``fit``

@@ -167,12 +167,22 @@ class Diagnostic:
         The resident factor goes to the host and into the leave-one-out library once; its inverse stays there until ``close()``."""
         if self.df is not None:
             raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out (df set) is not provided")
+        return self._loo_factor().loo(y, self._mean)
+
+    def _loo_factor(self):
         if self._L is None:
             raise ValueError("Diagnostic is closed")
         if self._loo is None:
             from .loo import LooFactor
             self._loo = LooFactor(self._L.to_host(), device=self._ctx.device, backend=self.backend)
-        return self._loo.loo(y, self._mean)
+        return self._loo
+
+    def kfold(self, y, folds):
+        R"""The leave-group-out predictions of y, (n_samples, [n_curves]): every point against the points outside its group
+        (``FoldResult``; ``folds`` as in ``LooFactor.folds``).  It shares the resident inverse factor with ``loo``."""
+        if self.df is not None:
+            raise NotImplementedError("kfold is the Gaussian leave-group-out; a Student-t one (df set) is not provided")
+        return self._loo_factor().folds(y, folds, self._mean)
 
     def loo_errors(self, y):
         R"""The standardised leave-one-out errors a_i / sqrt(p_i), shape (n_samples, [n_curves])."""
