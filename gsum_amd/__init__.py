@@ -5,7 +5,8 @@ Compute runs in libgsum_hip.so (hand-written HIP for gfx950, bound with ctypes);
 ``Diagnostic.variogram``) runs in its own libgsum_vario.so, and the reference distributions of ``GraphicalDiagnostic`` (``refdist``: column
 sort, percentile bands, interval coverage) in their own libgsum_refdist.so; the uncorrelated model ``TruncationPointwise`` (grid
 likelihood, credible-interval coverage) has its own libgsum_pointwise.so, the leave-one-out and leave-group-out diagnostics
-(``loo_from_factor``, ``kfold_from_factor``, ``Diagnostic.loo`` / ``.kfold``, ``ConjugateGaussianProcess.loo`` / ``.kfold``) their own libgsum_loo.so, and ``hpd``, ``hpd_pdf``, ``median_pdf`` and ``cartesian`` are
+(``loo_from_factor``, ``kfold_from_factor``, ``Diagnostic.loo`` / ``.kfold``, ``ConjugateGaussianProcess.loo`` / ``.kfold``) their own libgsum_loo.so, the Toeplitz likelihood path for stationary kernels on uniform one-dimensional grids
+(``structure="toeplitz"``, ``toeplitz_column``, ``toeplitz_gram``, ``uniform_grid_step``) its own libgsum_toep.so, and ``hpd``, ``hpd_pdf``, ``median_pdf`` and ``cartesian`` are
 the reference's host helpers.  matplotlib is imported by ``GraphicalDiagnostic``'s plot
 methods when they are called, never by importing this package.  There is no CPU path except where a class takes ``backend='cpu'``.
 """
@@ -22,6 +23,7 @@ from . import refdist
 from .graphical import GraphicalDiagnostic
 from .pointwise import TruncationPointwise
 from .loo import FoldResult, LooResult, kfold_from_factor, loo_from_factor, make_folds
+from .toeplitz import toeplitz_column, toeplitz_gram, uniform_grid_step
 from .stats import hpd, hpd_pdf, median_pdf, cartesian
 from .grid import shard_range, gather_flat, lml_grid_distributed, predict_distributed
 from ._lib import HipContext, HipGroup, KernelDesc, default_context, default_group, device_count, lab_context, load_library
@@ -32,5 +34,5 @@ __all__ = [
     "TruncationGP", "TruncationTP", "posterior_from_gram", "lml_from_gram", "lml_from_gram_batch", "student_lml_from_gram", "cov_factor", "describe_kernel", "describe_thetas", "make_gaussian_partial_sums",
     "make_gaussian_partial_sums_uniform", "make_gaussian_partial_sums_on_grid", "sample_mvn_cholesky", "shard_range", "gather_flat",
     "lml_grid_distributed", "Diagnostic", "pivoted_cholesky", "VariogramFourthRoot", "GraphicalDiagnostic", "refdist",
-    "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
+    "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "toeplitz_column", "toeplitz_gram", "uniform_grid_step", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
 ]

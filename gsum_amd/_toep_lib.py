@@ -1,0 +1,91 @@
+"""ctypes binding of libgsum_toep.so (C ABI: include/gsum_toep.h), the library of the Toeplitz likelihood path."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import threading
+
+import numpy as np
+
+from . import _sidelib
+from ._sidelib import DeviceHandle, _d, _i32
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libgsum_toep.so")
+
+_p = C.c_void_p
+_dp = C.POINTER(C.c_double)
+PROTOTYPES = {
+    "gsum_toep_last_error": (C.c_char_p, []),
+    "gsum_toep_open": (C.c_int, [C.c_int32, C.POINTER(_p)]),
+    "gsum_toep_close": (None, [_p]),
+    "gsum_toep_max_n": (C.c_int64, [_p]),
+    "gsum_toep_gram": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_times": (C.c_int, [_p, _dp, C.c_int32]),
+}
+PHASES = ("h2d", "schur", "gram", "d2h")
+MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
+
+
+def load_library(path: str | None = None):
+    """dlopen libgsum_toep.so and attach the prototypes.  Raises if it is absent (``python -m gsum_amd.build`` builds it)."""
+    return _sidelib.load(LIB_PATH, PROTOTYPES, path)
+
+
+def _check(lib, rc):
+    _sidelib.check(lib, rc, "gsum_toep_last_error")
+
+
+def max_n():
+    """The largest n ``DeviceToeplitz.gram`` takes (needs no device)."""
+    return int(load_library().gsum_toep_max_n(None))
+
+
+class DeviceToeplitz(DeviceHandle):
+    """A handle of libgsum_toep.so on one device: its stream and its buffers, which grow with the calls."""
+
+    _free = "gsum_toep_close"
+
+    def __init__(self, device):
+        self._lib = lib = load_library()
+        self._lock = threading.Lock()                                  # one call at a time: the buffers belong to the handle
+        h = C.c_void_p()
+        _check(lib, lib.gsum_toep_open(int(device), C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("the handle is closed")
+        return self._h
+
+    def gram(self, t, Z, n_sets):
+        """(G (m, n_sets, c, c), sum_log_diag (m,), info (m,) int32) of the first columns t (m, n) and the right-hand sides Z
+        (n, n_sets * c): gsum_toep_gram."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        Zf = np.asfortranarray(Z, dtype=np.float64)
+        m, n = t.shape
+        cols = Zf.shape[1] // n_sets
+        G = np.empty((m, n_sets, cols, cols))
+        sld = np.empty(m)
+        info = np.empty(m, dtype=np.int32)
+        with self._lock:
+            _check(self._lib, self._lib.gsum_toep_gram(self._handle(), _d(t), m, n, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info)))
+        return G, sld, info
+
+    def times(self, reset=False):
+        """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
+        ms = np.zeros(len(PHASES))
+        _check(self._lib, self._lib.gsum_toep_times(self._handle(), _d(ms), int(bool(reset))))
+        return dict(zip(PHASES, ms.tolist()))
+
+
+_handles = {}
+_handles_lock = threading.Lock()
+
+
+def default_handle(device):
+    """The process's one handle per device, opened on first use."""
+    with _handles_lock:
+        if device not in _handles:
+            _handles[device] = DeviceToeplitz(device)
+        return _handles[device]

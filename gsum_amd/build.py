@@ -15,6 +15,9 @@
 ``libgsum_loo.so``      the leave-one-out and leave-group-out diagnostics (include/gsum_loo.h): the inverse of a Cholesky factor, the
                         diagonal and the blocks of the precision matrix, (L L^T)^-1 R and the predictions of every group of a
                         partition from the points outside it.  Its own small library, built like the variogram's.
+``libgsum_toep.so``     the Toeplitz likelihood path (include/gsum_toep.h): the Schur recursion of a symmetric Toeplitz matrix in
+                        double-double arithmetic with the forward substitution beside it, and the Gram matrices of the solved
+                        columns.  Its own small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations
@@ -41,7 +44,7 @@ SIDE_SCAFFOLD = os.path.join(HERE, "csrc", "host", "sidelib.hip.h")      # the h
 SIDE = {name: (os.path.join(HERE, "csrc", f"gsum_{name}.hip"), os.path.join(HERE, "csrc", f"gsum_{name}.map"),
                os.path.join(HERE, "csrc", "kernels", f"{kernels}.hip.h"), os.path.join(ROOT, "include", f"gsum_{name}.h"),
                os.path.join(HERE, f"libgsum_{name}.so"))
-        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"), ("loo", "loo"))}
+        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"), ("loo", "loo"), ("toep", "toeplitz"))}
 
 
 def hipcc_path():
@@ -81,6 +84,10 @@ def build_pointwise(force: bool = False, verbose: bool = False) -> str:
 
 def build_loo(force: bool = False, verbose: bool = False) -> str:
     return build_side("loo", force, verbose)
+
+
+def build_toep(force: bool = False, verbose: bool = False) -> str:
+    return build_side("toep", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:

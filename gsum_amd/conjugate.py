@@ -520,7 +520,12 @@ class ConjugateGaussianProcess:
     corr_sqrt_ = corr_L_
 
     # -- log marginal likelihood (models.py:912-1039) --------------------------------------------
-    def log_marginal_likelihood(self, theta=None, eval_gradient=False, X=None, y=None):
+    def log_marginal_likelihood(self, theta=None, eval_gradient=False, X=None, y=None, structure=None):
+        """``structure=None``: the dense route (kernel build, Cholesky, solve).  ``structure="toeplitz"``: the value from the first
+        column of the kernel matrix alone (``gsum_amd.toeplitz``; a stationary kernel on a uniform one-dimensional grid, no
+        gradient): the likelihood of the exactly Toeplitz matrix of that column."""
+        if structure is not None:
+            return self._lml_structured(structure, [theta], eval_gradient, X, y)[0]
         if theta is None and self._fit:
             if eval_gradient:
                 raise ValueError("Gradient can only be evaluated for theta!=None")   # models.py:940-943
@@ -552,6 +557,32 @@ class ConjugateGaussianProcess:
             return -np.inf                                                           # models.py:970-972
         lml, _ = self._lml_gram(G[0], sld[0], X.shape[0])
         return lml
+
+    def _lml_structured(self, structure, thetas, eval_gradient, X, y):
+        """The values of ``log_marginal_likelihood(theta, structure=...)`` for several theta (None: the fitted / given kernel): one
+        first column per theta, one device call for all of them.  Everything the dense route would do silently differently is an error."""
+        if structure != "toeplitz":
+            raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+        if eval_gradient:
+            raise NotImplementedError('structure="toeplitz" has no gradient: tr(T^-1 dT) needs the diagonal sums of T^-1')
+        from .toeplitz import column_of_desc, toeplitz_gram, uniform_grid_step
+        self._check_decomposition()
+        kernel = self._active_kernel()
+        X = np.asarray(self.X_train_ if X is None else X, dtype=float)
+        y = self.y_train_ if y is None else y
+        if X.ndim != 2 or X.shape[1] != 1:
+            raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: X must have shape (n, 1), got {X.shape}')
+        uniform_grid_step(X)
+        if self._many_curves(y):
+            raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
+        Z = self._rhs(X, y)
+        given = [t for t in thetas if t is not None]
+        descs = iter(describe_thetas(kernel, given, 1)) if given else iter(())
+        ctx = self._context()
+        cols = np.stack([column_of_desc(ctx, next(descs) if t is not None else describe_kernel(kernel, 1), X, self.nugget) for t in thetas])
+        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend)
+        vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
+        return np.where(info != 0, -np.inf, vals)                                    # models.py:970-972
 
     def _lml_many_curves(self, desc, kernel, theta, eval_gradient, X, y):
         """log_marginal_likelihood for more than GSUM_MAX_RHS - 1 curves: one device call per chunk of curves (see _rhs_chunks)."""
@@ -611,10 +642,13 @@ class ConjugateGaussianProcess:
             raise ValueError("Unknown optimizer %s." % self.optimizer)
         return theta_opt, func_min
 
-    def log_marginal_likelihood_batch(self, thetas, X=None, y=None):
+    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None):
         """``log_marginal_likelihood(theta, eval_gradient=True)`` for several ``theta`` at once: [(lml, grad), ...].  The
         evaluations are independent and go to the device as one pipelined batch (gsum_lml_grad_batch); every entry equals
-        the single call's result bit for bit."""
+        the single call's result bit for bit.  ``structure="toeplitz"``: the values alone, as an array with one entry per theta
+        (``log_marginal_likelihood(theta, structure="toeplitz")``; that route has no gradient), from one device call."""
+        if structure is not None:
+            return self._lml_structured(structure, [np.atleast_1d(np.asarray(t, dtype=float)) for t in thetas], False, X, y)
         self._check_decomposition()
         base = self._active_kernel()
         X = np.asarray(self.X_train_ if X is None else X, dtype=float)

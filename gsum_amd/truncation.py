@@ -286,7 +286,7 @@ class TruncationGP:
         return coeff_log_like - det_factor
 
     def log_marginal_likelihood_grid(self, thetas, ratio_kws_list, scales=None, X=None, y=None, orders=None, mode="full",
-                                     shard=None, devices=None, gather="host", _ctx=None):
+                                     shard=None, devices=None, gather="host", _ctx=None, structure=None):
         """Likelihood surface over (ratio settings) x (thetas) [x (prior scales)].
 
         ``scales=None``: ``out[i, j]`` equals ``self.log_marginal_likelihood(thetas[j], **ratio_kws_list[i])``.
@@ -309,7 +309,18 @@ class TruncationGP:
         (``gsum_amd.HipGroup``), merged into one surface that equals the one-device result bit for bit.  ``gather="rccl"``
         additionally exchanges the shards between the devices with one in-place ``ncclAllGather`` (``gsum_group_allgather``;
         every rank's gathered surface is compared with rank 0's) instead of merging on the host only.
+        ``structure="toeplitz"`` (default None: the dense routes above) takes the surface from the first column of every theta's
+        kernel matrix (``gsum_amd.toeplitz``): a stationary kernel on a uniform one-dimensional grid, one Schur
+        recursion per theta with every ratio setting as a set of right-hand sides, O(n^2) per point and no n x n matrix.  It is the
+        likelihood of the exactly Toeplitz matrix of that column; both modes give the same numbers, ``shard`` splits whole thetas, and
+        ``devices=`` / ``gather=``, more than 15 curves, a non-uniform X and a non-stationary kernel are errors, never a dense evaluation.
         """
+        if structure is not None:
+            if structure != "toeplitz":
+                raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+            if devices is not None or gather != "host" or _ctx is not None:
+                raise ValueError('structure="toeplitz" runs on one device: devices= and gather= are not supported (shard= is)')
+            return self._grid_toeplitz(thetas, ratio_kws_list, scales, X, y, orders, mode, shard)
         if devices is not None:
             if shard is not None:
                 raise ValueError("shard= (one process per GPU) and devices= (one process, several GPUs) exclude each other")
@@ -462,6 +473,54 @@ class TruncationGP:
             raise ValueError('mode must be "full" or "reuse"')
         return shaped(out)
 
+
+    def _grid_toeplitz(self, thetas, ratio_kws_list, scales, X, y, orders, mode, shard):
+        """The surface of ``structure="toeplitz"``: one first column per theta of this rank, one set [coefficients | 1] per ratio
+        setting, one device call; the prior scales only enter the host algebra."""
+        from .grid import owned_points
+        from .toeplitz import column_of_desc, toeplitz_gram, uniform_grid_step
+        if mode not in ("full", "reuse"):
+            raise ValueError('mode must be "full" or "reuse"')
+        X = self.X_train_ if X is None else X
+        y = self.y_train_ if y is None else y
+        orders = self.orders_ if orders is None else orders
+        Xd = np.asarray(X, dtype=float)
+        if Xd.ndim != 2 or Xd.shape[1] != 1:
+            raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: X must have shape (n, 1), got {Xd.shape}')
+        uniform_grid_step(Xd)
+        if self._grid_many_curves(orders):
+            raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves')
+        gp = self.coeffs_process
+        ni, nj = len(ratio_kws_list), len(thetas)
+        if scales is None:
+            ns, scale_vals = 1, None
+        else:
+            scale_vals = np.atleast_1d(np.asarray(scales, dtype=float))
+            if scale_vals.ndim != 1 or scale_vals.size == 0:
+                raise ValueError('scales must be a non-empty 1d sequence of prior standard deviations')
+            ns = scale_vals.size
+        out = np.full((ni, nj, ns), np.nan)
+        mine = owned_points(ni, nj, ns, *(shard or (0, 1)), partition="theta")
+        if len(mine) and ni:
+            n_pts = Xd.shape[0]
+            js = np.unique((np.asarray(mine, dtype=np.int64) // ns) % nj)
+            ctx = gp._context()
+            descs = describe_thetas(gp._active_kernel(), [thetas[j] for j in js], 1)
+            cols = np.stack([column_of_desc(ctx, d, Xd, gp.nugget) for d in descs])
+            Zs, dets = self._rhs_rows(Xd, y, orders, [kws if isinstance(kws, dict) else {"ratio": kws} for kws in ratio_kws_list])
+            k = Zs.shape[2]
+            G, sld, info = toeplitz_gram(cols, Zs.transpose(1, 0, 2).reshape(n_pts, ni * k), ni, device=gp.device, backend=gp.backend)
+            # (thetas, rows, scales) entries of the host algebra
+            Gb = np.broadcast_to(G[:, :, None], (len(js), ni, ns, k, k)).reshape(-1, k, k)
+            sb = np.broadcast_to(sld[:, None, None], (len(js), ni, ns)).reshape(-1)
+            if scale_vals is None:
+                vals = gp._lml_gram_batch(Gb, sb, n_pts)
+            else:
+                vals = gp._lml_gram_batch_sd(Gb, sb, n_pts, np.broadcast_to(scale_vals, (len(js), ni, ns)).reshape(-1))
+            vals = vals.reshape(len(js), ni, ns) - dets[None, :, None]
+            vals = np.where((info != 0)[:, None, None], -np.inf, vals)
+            out[:, js, :] = vals.transpose(1, 0, 2)
+        return out if scales is not None else out[:, :, 0]
 
     def _grid_many_curves(self, orders):
         orders = np.asarray(self.orders_ if orders is None else orders)
