@@ -1,4 +1,6 @@
 // libgsum_toep.so: the C ABI of include/gsum_toep.h (the Toeplitz likelihood path).  Kernels: kernels/toeplitz.hip.h.
+#include <cstdio>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -20,7 +22,7 @@ constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y
 
 struct gsum_toep : Handle {
     DevBuf<double, true> t, Z, Y, G, sld;
-    DevBuf<int32_t, true> info;
+    DevBuf<int32_t, true> info, ze;
     double ms[kPhases] = {0, 0, 0, 0};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
     ~gsum_toep() {
@@ -85,13 +87,13 @@ void launch_schur(gsum_toep* h, const double* t, int n, int ncols, int64_t m, do
     const dim3 grid((unsigned)((ncols + C - 1) / C), (unsigned)m);
     hipStream_t st = h->stream;
     if (n <= gt::kThreads)
-        gt::k_schur<1, 16, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, ncols, Y, sld, info);
+        gt::k_schur<1, 16, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
     else if (n <= 4 * gt::kThreads)
-        gt::k_schur<4, 12, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, ncols, Y, sld, info);
+        gt::k_schur<4, 12, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
     else if (n <= 8 * gt::kThreads)
-        gt::k_schur<8, 5, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, ncols, Y, sld, info);
+        gt::k_schur<8, 5, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
     else
-        gt::k_schur<16, 3, true><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, ncols, Y, sld, info);
+        gt::k_schur<16, 3, true><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
     SL_LAUNCHED("k_schur");
 }
 
@@ -123,6 +125,17 @@ GT_API int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, c
         if (n_sets > 65535) throw Error("gsum_toep_gram: n_sets must be <= 65535, got " + std::to_string(n_sets));
         if (n_sets * cols > (((int64_t)1 << 31) - 1) / n)
             throw Error("gsum_toep_gram: n * n_sets * cols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(n_sets) + " x " + std::to_string(cols));
+        // The right-hand sides are normalised on the device (k_colexp); the scale of T reaches the fp32 correction word through
+        // lo(L) ~ 2^-53 sqrt(t0) and y ~ 1 / sqrt(t0), which stay far inside fp32's range for t0 within 2^-64 .. 2^64.
+        for (int64_t i = 0; i < m; ++i) {
+            const double t0 = t[i * n];
+            if (t0 > 0.0 && t0 < INFINITY && (t0 < 0x1p-64 || t0 > 0x1p64)) {
+                char got[32];
+                snprintf(got, sizeof got, "%g", t0);
+                throw Error("gsum_toep_gram: t[0] must lie within 2^-64 .. 2^64 (scale t by a power of 4 and G and sum_log_diag with it), got " +
+                            std::string(got) + " in first column " + std::to_string(i));
+            }
+        }
         const int ncols = (int)(n_sets * cols);
         const size_t per_theta = (size_t)n * ncols;                            // doubles of Y per first column
         const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (per_theta * sizeof(double)))));
@@ -134,17 +147,22 @@ GT_API int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, c
             h->G.reserve(gsz * m);
             h->sld.reserve((size_t)m);
             h->info.reserve((size_t)m);
+            h->ze.reserve((size_t)ncols);
             hipStream_t st = h->stream;
             timed(h, kH2D, [&] {
                 SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
                 SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
+            });
+            timed(h, kSchur, [&] {
+                gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
+                SL_LAUNCHED("k_colexp");
             });
             for (int64_t lo = 0; lo < m; lo += step) {
                 const int64_t cnt = std::min(step, m - lo);
                 timed(h, kSchur, [&] { launch_schur(h, h->t.p + lo * n, (int)n, ncols, cnt, h->Y.p, h->sld.p + lo, h->info.p + lo); });
                 timed(h, kGram, [&] {
                     gt::k_gram<<<dim3((unsigned)cols, (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(h->Y.p, (int)n, cols, (int)n_sets,
-                                                                                                         h->info.p + lo, h->G.p + gsz * lo);
+                                                                                                         h->ze.p, h->info.p + lo, h->G.p + gsz * lo);
                     SL_LAUNCHED("k_gram");
                 });
             }

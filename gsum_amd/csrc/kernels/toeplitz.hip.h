@@ -14,6 +14,10 @@
 //   written to Y (row k), so a column's values do not depend on which other columns share its chunk.
 //   An element at or above the pivot is never written again, so at the end u[i] holds L[i, i]: their logarithms are summed in a
 //   fixed order (E per thread, then a binary tree over the threads).
+// k_colexp: the binary exponent of the largest finite magnitude of each right-hand-side column, one wave per column.  k_schur loads a
+//   column scaled by that power of two (exact), so that its largest entry lies in [1, 2) and y_k and the correction word stay inside
+//   fp32's range whatever the scale of Z; k_gram scales G[a, b] back by the two exponents (exact short of over- and underflow of G
+//   itself).  A column of zeros, or with an infinite entry, is taken as it is.
 // k_gram: G[a, b] = sum_k Y[k, a] Y[k, b] of one set of columns, one wave per (first column, set, a): lane l sums the rows l, l + 64,
 //   ... in order, then a butterfly over the lanes.  The order depends on n alone.
 // Every value is written with ordinary vector stores; there are no atomics.
@@ -86,11 +90,24 @@ __device__ __forceinline__ dd dd_rsqrt(dd a) {
     return quick_two_sum(x, x * r.h * 0.5);
 }
 
-// Y is (m, n, ncols) row-major; Z is column-major n x ncols; t is (m, n).  grid = (chunks, m), block = kThreads.
+// ze[col] = ilogb(max_k |Z[k, col]|) over the finite entries, 0 where that maximum is zero or infinite.  grid = ncols, block = kWave.
+__global__ __launch_bounds__(kWave) void k_colexp(const double* __restrict__ Z, int n, int32_t* __restrict__ ze) {
+    const int lane = threadIdx.x;
+    const double* z = Z + (int64_t)blockIdx.x * n;
+    double mx = 0.0;
+    for (int k = lane; k < n; k += kWave) mx = fmax(mx, fabs(z[k]));       // fmax drops a NaN
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) mx = fmax(mx, __shfl_xor(mx, off, kWave));
+    if (lane == 0) ze[blockIdx.x] = (mx > 0.0 && mx < INFINITY) ? ilogb(mx) : 0;
+}
+
+// Y is (m, n, ncols) row-major; Z is column-major n x ncols, ze its column exponents (k_colexp); t is (m, n).  grid = (chunks, m),
+// block = kThreads.  Y holds the solved columns of the scaled Z.
 // LDS: pub[buffer] = {u[k].h, u[k].l, v[k+1].h, v[k+1].l, z[k][0..C)}, edge[buffer][thread] = the thread's last u element.
 template <int E, int C, bool VL>
-__global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t, int n, const double* __restrict__ Z, int ncols,
-                                                     double* __restrict__ Y, double* __restrict__ sld, int32_t* __restrict__ info) {
+__global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t, int n, const double* __restrict__ Z,
+                                                     const int32_t* __restrict__ ze, int ncols, double* __restrict__ Y,
+                                                     double* __restrict__ sld, int32_t* __restrict__ info) {
     __shared__ double s_pub[2][4 + C];
     __shared__ double s_edge[2][kThreads][2];
     __shared__ alignas(16) double s_v[VL ? E : 1][VL ? kThreads : 1][2];      // VL: v lives here, element e of thread tid at [e][tid]
@@ -125,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
             set_v(e, i > 0 ? u : dd{0.0, 0.0});
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                z[e][c] = (i < n && c < nc) ? Z[(int64_t)(col0 + c) * n + i] : 0.0;
+                z[e][c] = (i < n && c < nc) ? ldexp(Z[(int64_t)(col0 + c) * n + i], -ze[col0 + c]) : 0.0;
                 zc[e][c] = 0.f;
             }
             if (i == 0) {
@@ -221,9 +238,9 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
     }
 }
 
-// G is (m, n_sets, cols, cols).  grid = (cols, n_sets, m), block = kWave.
-__global__ __launch_bounds__(kWave) void k_gram(const double* __restrict__ Y, int n, int cols, int n_sets, const int32_t* __restrict__ info,
-                                                 double* __restrict__ G) {
+// G is (m, n_sets, cols, cols), scaled back by the column exponents ze.  grid = (cols, n_sets, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_gram(const double* __restrict__ Y, int n, int cols, int n_sets, const int32_t* __restrict__ ze,
+                                                 const int32_t* __restrict__ info, double* __restrict__ G) {
     const int a = blockIdx.x, set = blockIdx.y, lane = threadIdx.x;
     const int64_t theta = blockIdx.z;
     const int ncols = n_sets * cols;
@@ -248,7 +265,7 @@ __global__ __launch_bounds__(kWave) void k_gram(const double* __restrict__ Y, in
         double x = acc[bcol];
 #pragma unroll
         for (int off = 1; off < kWave; off <<= 1) x += __shfl_xor(x, off, kWave);
-        if (lane == 0 && bcol < cols) g[bcol] = x;
+        if (lane == 0 && bcol < cols) g[bcol] = ldexp(x, ze[set * cols + a] + ze[set * cols + bcol]);
     }
 }
 

@@ -154,7 +154,9 @@ def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None):
     Z, (n, n_sets * c) in ``n_sets`` sets of c <= 16 columns: ``G[s] = Z_s^T T^-1 Z_s`` (c x c), ``sum_log_diag = sum_j log L_jj`` of
     ``T = L L^T`` and ``info`` = 0, or the 1-based step at which the pivot of the recursion stops being finite and positive (then G and
     sum_log_diag are NaN).  Shapes: t (n,) gives G (n_sets, c, c) and two scalars; t (m, n) gives (m, n_sets, c, c), (m,), (m,).
-    ValueError beyond ``toeplitz_max_n()`` on the device: nothing falls back to a dense evaluation."""
+    ValueError beyond ``toeplitz_max_n()`` on the device: nothing falls back to a dense evaluation.  On the device the scale of Z is
+    free (each column is normalised by a power of two and G scaled back, both exactly), while a positive finite ``t[0]`` outside
+    2^-64 .. 2^64 is a ValueError: scale t by a power of 4 instead."""
     t = np.asarray(t, dtype=float)
     single = t.ndim == 1
     t2 = np.ascontiguousarray(t[None] if single else t)

@@ -23,7 +23,12 @@
  *   the high word of each entry of L, and what the low words contribute is summed beside each residual in an fp32 word and taken
  *   off at its pivot; every sum has a fixed order that depends on n alone: the result of a (first column, set) is bitwise
  *   reproducible and does not depend on m, on the other sets, on their order or on how the columns are chunked.
- *   Refused: null pointers, m, n, n_sets < 1, cols outside 1 .. GSUM_TOEP_MAX_COLS, n > gsum_toep_max_n, n * n_sets * cols >= 2^31.
+ *   Range: each right-hand-side column is scaled on the device by the power of two that brings its largest finite magnitude into
+ *   [1, 2), and G is scaled back, both exactly, so the scale of Z is free as far as G itself is representable.  The scale of T is not
+ *   normalised: the fp32 word holds products of lo(L) ~ 2^-53 sqrt(t[0]) and y ~ 1 / sqrt(t[0]), and a positive finite t[0] outside
+ *   2^-64 .. 2^64 is refused (scale t by a power of 4: G scales by its inverse, sum_log_diag moves by n / 2 times its logarithm).
+ *   Refused: null pointers, m, n, n_sets < 1, cols outside 1 .. GSUM_TOEP_MAX_COLS, n > gsum_toep_max_n, n * n_sets * cols >= 2^31,
+ *   a positive finite t[0] outside 2^-64 .. 2^64.
  *
  * gsum_toep_times: ms[0..3] = device time in milliseconds (HIP events) the handle has spent so far in: 0 host-to-device copies,
  *   1 the recursion with its forward substitution, 2 the Gram matrices, 3 device-to-host copies.  reset != 0 zeroes them.

@@ -52,9 +52,56 @@ def test_ill_conditioned_goldens(name):
     Measured on an MI355X, G relative to max|G| (device / numpy / cpu): rbf_n64 6.4e-13 / 1.1e-6 / 8.6e-10, rbf_n128 7.5e-13 / 1.4e-6 /
     3.5e-9, matern52_n64 3.1e-15 / 2.5e-11 / 2.5e-15, matern52_n128 2.4e-14 / 2.5e-9 / 2.5e-13, rbf_white_n128 3.5e-14 / 2.2e-8 / 2.0e-11;
     sum_log_diag 0 to 2e-16.  matern52_n64 is the case that needs the correction word for the low words of L:
-    without it the device sits at 4.2e-14, above 4 x max(cpu, floor) = 2.8e-14."""
+    without it the device sits at 4.2e-14, above 4 x max(cpu, floor) = 2.8e-14.
+    The goldens of toeplitz_classes.json (the smallest n of the classes with 4, 8 and 16 elements per thread, the last with v in LDS
+    and two column chunks; truth by the mpmath Schur recursion): matern52_n513 (cond 1.4e12) 3.6e-14 / 9.1e-7 / 4.9e-9, rbf_n2049
+    (nugget 1e-8, cond 9.0e10) 1.1e-13 / 3.4e-8 / 3.7e-10, matern52_n4097 (cond 1.7e13) 1.5e-13 / 3.7e-6 / 1.2e-8; sum_log_diag 0."""
     d, d_np, d_cpu = tc.check_ill("hip", name)
     record_parity(f"toeplitz/golden/{name}", G=d[0], sld=d[1], numpy_G=d_np[0], numpy_sld=d_np[1], cpu_G=d_cpu[0], cpu_sld=d_cpu[1])
+
+
+@pytest.mark.parametrize("n", [n for n in tc.SIZES if n >= 3])
+def test_arfima_sizes(n):
+    """ARFIMA(0, d, 0), d over (0.4, -0.3): reflection coefficients d / (k - d), so every step rotates and v, its LDS home in the
+    largest class and the publication of v[k+2] carry numbers instead of zeros.  sum_log_diag against the closed form at every size.
+    G against an mpmath golden at n = 513, 2049, 4097 and 8192 (all four were generated); at the other sizes against the cpu backend's
+    G within the sum of the two bounds, 2 * 4 * 64 * 2^-53 of max|G|, which is a comparison of two implementations and not a truth."""
+    record_parity(f"toeplitz/arfima/n{n}", **tc.check_arfima("hip", n))
+
+
+@pytest.mark.parametrize("n", tc.LATE_SIZES)
+def test_late_failures(n):
+    """The first failing step placed at the first steps, around a thread boundary (E, J E), and in the last two steps of the classes
+    with E = 4, 8 and 16 generator elements per thread."""
+    info = tc.check_late_failures("hip", n)
+    record_parity(f"toeplitz/late_failures/n{n}", info=info)
+
+
+def test_first_columns_in_three_launches():
+    info = tc.check_chunk_loop("hip")
+    record_parity("toeplitz/chunk_loop", info=info, **tc.CHUNKED)
+
+
+def test_scaling_is_bitwise():
+    record_parity("toeplitz/scaling", sld_shift_eps=tc.check_scaling("hip") / tc.EPS)
+
+
+@pytest.mark.parametrize("a", tc.FAR)
+def test_far_scaling(a):
+    """Right-hand sides scaled by 2^140 and 2^-140, outside what the fp32 correction word and the fp32 copy of y_k hold.  Before the
+    columns were normalised on the device (k_colexp) the library returned non-finite G with info 0 at +140 and lost the correction at
+    -140 (read from the code: (float)y overflows, ulf * yf underflows)."""
+    d = tc.check_far_scaling("hip", a)
+    record_parity(f"toeplitz/far_scaling/a{a}", G=d[0], sld=d[1])
+
+
+def test_scale_of_t_outside_the_stated_range_is_refused():
+    t = tc.kms_column(8, 0.5)
+    for s in (2.0 ** -66, 2.0 ** 66):
+        with pytest.raises(ValueError, match=r"t\[0\] must lie within"):
+            gm.toeplitz_gram(s * t, np.ones((8, 1)))
+    for s in (2.0 ** -64, 2.0 ** 64):
+        assert gm.toeplitz_gram(s * t, np.ones((8, 1)))[2] == 0
 
 
 @pytest.mark.parametrize("kernel", [RBF(0.2), Matern(0.3, nu=2.5), Matern(0.3, nu=0.5), 2.0 * RBF(0.2) + WhiteKernel(1e-3)], ids=str)

@@ -38,6 +38,75 @@ def test_ill_conditioned_goldens(name):
     tc.check_ill("cpu", name)
 
 
+@pytest.mark.parametrize("n", [n for n in tc.SIZES if n >= 3])
+def test_arfima_sizes(n):
+    """ARFIMA(0, d, 0), d over (0.4, -0.3): every step of the recursion rotates.  sum_log_diag within the floor of the closed form (so
+    rounding t to fp64 does not move the answer); G within the rule of the mpmath golden at n = 513, 2049, 4097 and 8192."""
+    tc.check_arfima("cpu", n)
+
+
+def test_arfima_goldens_cover_the_upper_classes_and_the_limit():
+    assert tc.arfima_golden_sizes() == [513, 2049, 4097, 8192]
+    assert [c["n"] for c in tc.classes_golden()["ill"]] == [513, 2049, 4097]
+    assert os.path.getsize(tc.CLASSES_GOLDEN) < 473 * 1024
+
+
+def test_arfima_reflection_coefficients_never_vanish():
+    """What makes the family a test of the rotation: the coefficients of the cpu recursion's own column are d / (k - d), none zero; the
+    Kac-Murdock-Szego column's are [rho, 0, 0, ...], so after its first step v is zero and a step only shifts u."""
+    def coefficients(t):
+        u = np.asarray(t, dtype=tc.LD) / np.sqrt(tc.LD(t[0]))
+        v = u.copy()
+        v[0] = 0
+        out = []
+        for k in range(len(t) - 1):
+            rho = v[k + 1] / u[k]
+            out.append(float(rho))
+            ic = 1 / np.sqrt((1 - rho) * (1 + rho))
+            us, vv = u[k:-1].copy(), v[k + 1:].copy()
+            u[k + 1:], v[k + 1:] = (us - rho * vv) * ic, (vv - rho * us) * ic
+        return np.array(out)
+    n = 200
+    for d in tc.DS + (0.25,):
+        g = coefficients(tc.arfima_column(n, d))
+        assert np.max(np.abs(g - d / (np.arange(1, n) - d))) <= 4e-16 and np.min(np.abs(g)) > 1e-3
+        E = tc.arfima_energies(n, d)
+        assert np.allclose(np.cumprod(1 - g ** 2), np.asarray(E[1:], dtype=float), rtol=1e-13, atol=0)
+    g = coefficients(tc.kms_column(n, 0.5))
+    assert g[0] == 0.5 and np.max(np.abs(g[1:])) == 0.0
+
+
+@pytest.mark.parametrize("n", tc.LATE_SIZES)
+def test_late_failures(n):
+    ps, p_nan = tc.late_positions(n)
+    info = tc.check_late_failures("cpu", n)
+    assert sorted(info) == sorted([0] + [p + 1 for p in ps] + [p_nan + 1]) and len(set(ps)) == len(ps)
+
+
+def test_chunked_shape_arithmetic():
+    """The shape of the device test of the first-column loop, in the library's arithmetic (gsum_toep.hip): one first column per launch,
+    so three launches; one set fewer and two would fit; every other shape of the suite goes through in one launch."""
+    s = tc.CHUNKED
+    ncols = s["n_sets"] * s["c"]
+    assert tc.first_columns_per_launch(s["n"], ncols, s["m"]) == 1
+    assert tc.first_columns_per_launch(s["n"], ncols - s["c"], s["m"]) == 2
+    assert s["n"] * ncols < 2 ** 31 and s["n_sets"] <= 65535
+    assert 128 << 20 < s["n"] * ncols * 8 < 130 << 20
+    for n, c, n_sets, m in tc.SHAPES:
+        assert tc.first_columns_per_launch(n, c * n_sets, m) == m
+    src = open(os.path.join(ROOT, "gsum_amd", "csrc", "gsum_toep.hip")).read()
+    assert "kYBudget = (size_t)256 << 20" in src and tc.Y_BUDGET == 256 << 20
+
+
+def test_scaling():
+    tc.check_scaling("cpu")
+
+
+@pytest.mark.parametrize("a", tc.FAR)
+def test_far_scaling(a):
+    tc.check_far_scaling("cpu", a)
+
+
 def test_uniform_grid_step():
     for scale in (1.0, 3.7, 1e-3, 123456.789):
         for n in (2, 5, 100, 8192):

@@ -4,7 +4,10 @@
     (diagonal [1, 1 + rho^2, ..., 1 + rho^2, 1] / (1 - rho^2), off-diagonal -rho / (1 - rho^2)), so any z^T T^-1 z' is an O(n) sum, taken
     here in numpy.longdouble.  Bound: the project's floor 64 * 2^-53, relative to max|G| and to max(1, |sum_log_diag|), times the factor
     by which the cpu backend's own distance exceeds the floor, capped at 4.
-(b) Failures, (c) bitwise properties, (d) ill-conditioned goldens (tests/golden/toeplitz.json, mpmath truth).
+(b) Failures, (c) bitwise properties, (d) ill-conditioned goldens (tests/golden/toeplitz.json at n = 64 and 128, toeplitz_classes.json at
+    the smallest n of the device kernel's three upper size classes; mpmath truth).
+(e) A closed-form family whose every step rotates, ARFIMA(0, d, 0); (f) failures at late steps, at thread boundaries and in the last
+    step; (g) the host loop over chunks of first columns; (h) scaling of t and Z, and right-hand sides beyond fp32's range.
 Every check takes the backend and returns what it measured, so the GPU tests can record it."""
 import functools
 import json
@@ -146,8 +149,13 @@ def golden():
         return json.load(f)
 
 
+def ill_cases():
+    """The ill-conditioned goldens: those of toeplitz.json (n = 64, 128) and those of toeplitz_classes.json (n = 513, 2049, 4097)."""
+    return golden()["ill"] + classes_golden()["ill"]
+
+
 def ill_names():
-    return [c["name"] for c in golden()["ill"]]
+    return [c["name"] for c in ill_cases()]
 
 
 def hex_column(case):
@@ -157,7 +165,7 @@ def hex_column(case):
 @functools.lru_cache(maxsize=None)
 def _ill_yardsticks(name):
     """(t, Z, truth G, truth sum_log_diag, distances of numpy's fp64 Cholesky of the same T, distances of the cpu backend)."""
-    case = [c for c in golden()["ill"] if c["name"] == name][0]
+    case = [c for c in ill_cases() if c["name"] == name][0]
     t, Z = hex_column(case), rhs_columns(case["n"], case["cols"])
     Gt, st = np.array(case["G"]), case["sum_log_diag"]
     L = np.linalg.cholesky(toeplitz(t))
@@ -181,6 +189,215 @@ def check_ill(backend, name):
         assert d[k] <= max(d_np[k], FLOOR), (name, k, d, d_np)
         assert d[k] <= 4 * max(d_cpu[k], FLOOR), (name, k, d, d_cpu)
     return d, d_np, d_cpu
+
+
+# ---- (e) ARFIMA(0, d, 0): a closed-form family whose every step rotates -------------------------------------------------------------
+# t_0 = 1, t_k = t_{k-1} (k - 1 + d) / (k - d) has the reflection coefficients gamma_k = d / (k - d): none vanishes, they decay like 1 / k.
+# The KMS family above is an AR(1) process: gamma_1 = rho and every later coefficient is exactly 0, so after the first step of the
+# recursion v is identically zero and the rotation a pure shift.  This family is the accuracy test of the rotation itself.
+DS = (0.4, -0.3)
+CLASSES_GOLDEN = os.path.join(os.path.dirname(GOLDEN), "toeplitz_classes.json")
+
+
+def arfima_column(n, d):
+    """The autocovariances of ARFIMA(0, d, 0) scaled to t_0 = 1, by +, -, *, / of Python floats in this order: bit-reproducible."""
+    t = [1.0]
+    for k in range(1, n):
+        t.append(t[-1] * (k - 1 + d) / (k - d))
+    return np.array(t)
+
+
+def arfima_energies(n, d):
+    """E_p = t_0 prod_{k <= p} (1 - gamma_k^2), p = 0 .. n - 1 (numpy.longdouble): the squared pivots of the recursion."""
+    k = np.arange(1, n, dtype=LD)
+    g = LD(d) / (k - LD(d))
+    return np.concatenate([[LD(1)], np.cumprod((1 - g) * (1 + g))])
+
+
+def arfima_sum_log_diag(n, d):
+    """sum_j log L_jj = 1/2 sum_{k=1}^{n-1} (n - k) log1p(-gamma_k^2) in numpy.longdouble, rounded to fp64."""
+    k = np.arange(1, n, dtype=LD)
+    g = LD(d) / (k - LD(d))
+    return float(np.sum((n - k) * np.log1p(-g * g)) / 2)
+
+
+@functools.lru_cache(maxsize=None)
+def classes_golden():
+    with open(CLASSES_GOLDEN) as f:
+        return json.load(f)
+
+
+@functools.lru_cache(maxsize=None)
+def _arfima_inputs(n):
+    """(t (2, n) with d over DS, Z (n, 4), closed-form sum_log_diag per first column, golden G (2, 4, 4) or None)."""
+    t = np.stack([arfima_column(n, d) for d in DS])
+    Z = rhs_columns(n, 4)
+    gold = {c["d"]: np.array(c["G"]) for c in classes_golden()["arfima"] if c["n"] == n}
+    t.setflags(write=False)
+    Z.setflags(write=False)
+    return t, Z, [arfima_sum_log_diag(n, d) for d in DS], (np.stack([gold[d] for d in DS]) if gold else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _arfima_results(backend, n):
+    t, Z, _, _ = _arfima_inputs(n)
+    G, sld, info = gm.toeplitz_gram(t, Z, 1, backend=backend)
+    assert G.shape == (2, 1, 4, 4) and not info.any(), info
+    assert np.array_equal(G, G.transpose(0, 1, 3, 2))
+    G.setflags(write=False)
+    return G[:, 0], sld
+
+
+def _rule(cpu):
+    """The bound of (a): the floor times the factor by which the cpu backend exceeds it, at most 4."""
+    return FLOOR * min(4.0, max(1.0, cpu / FLOOR))
+
+
+def arfima_golden_sizes():
+    return sorted({c["n"] for c in classes_golden()["arfima"]})
+
+
+def check_arfima(backend, n):
+    """(e): sum_log_diag against the closed form at every size, under the rule of (a); the cpu backend itself within the floor (that
+    is: rounding t to fp64 does not move the answer).  G against the mpmath golden of tests/golden/toeplitz_classes.json where there is
+    one (n = 513, 2049, 4097, 8192: the smallest n of the three upper size classes and the limit), under the same rule.  At the other
+    sizes G has no truth: the backend is held to the cpu backend's G within the sum of the two bounds, 2 * 4 * 64 * 2^-53 of max|G|.
+    That is a comparison of two implementations of one recursion, not a truth."""
+    t, Z, st, Gt = _arfima_inputs(n)
+    G, sld = _arfima_results(backend, n)
+    Gc, sc = _arfima_results("cpu", n)
+    d_s = max(abs(sld[i] - st[i]) / max(1.0, abs(st[i])) for i in range(2))
+    c_s = max(abs(sc[i] - st[i]) / max(1.0, abs(st[i])) for i in range(2))
+    out = dict(sld_eps=d_s / EPS, cpu_sld_eps=c_s / EPS)
+    if Gt is not None:
+        d_g = max(float(np.max(np.abs(G[i] - Gt[i])) / np.max(np.abs(Gt[i]))) for i in range(2))
+        c_g = max(float(np.max(np.abs(Gc[i] - Gt[i])) / np.max(np.abs(Gt[i]))) for i in range(2))
+        out.update(G_eps=d_g / EPS, cpu_G_eps=c_g / EPS)
+    else:
+        d_g = max(float(np.max(np.abs(G[i] - Gc[i])) / np.max(np.abs(Gc[i]))) for i in range(2))
+        out.update(G_vs_cpu_eps=d_g / EPS)
+    print(f"toeplitz arfima {backend} n={n}: " + ", ".join(f"{k} {v:.2f}" for k, v in out.items()))
+    assert c_s <= FLOOR, (n, c_s)
+    assert d_s <= _rule(c_s), (n, d_s, c_s)
+    if Gt is not None:
+        assert d_g <= _rule(c_g), (n, d_g, c_g)
+    else:
+        assert d_g <= 2 * 4 * FLOOR, (n, d_g)
+    return out
+
+
+# ---- (f) failures at late steps, next to thread boundaries and in the last step ------------------------------------------------------
+LATE_SIZES = (513, 2049, 4097)
+
+
+def elements_per_thread(n):
+    """The device kernel's generator elements per thread (E) in the size class of n."""
+    return 1 if n <= 512 else 4 if n <= 2048 else 8 if n <= 4096 else 16
+
+
+def late_positions(n):
+    E = elements_per_thread(n)
+    J = (n // E) // 2
+    return [1, 2, E - 1, E, E + 1, J * E - 1, J * E, J * E + 1, n - 2, n - 1], J * E + 1
+
+
+def check_late_failures(backend, n, d=0.25):
+    """(f): gamma_p is affine in t_p with the slope 1 / E_{p-1}, so adding 1.5 E_{p-1} to t_p of an ARFIMA column makes |gamma_p| about
+    1.5 and leaves the earlier coefficients alone: info == p + 1.  The positions are the first steps, those around the first thread
+    boundary (E) and around one in the middle (J E), and the last two; a NaN at t[J E + 1] fails at J E + 2.  All bad columns go in one
+    call around the unedited one, which must come out bit for bit as from a call of its own."""
+    good = arfima_column(n, d)
+    En = arfima_energies(n, d)
+    ps, p_nan = late_positions(n)
+    bad = []
+    for p in ps:
+        t = good.copy()
+        t[p] += 1.5 * float(En[p - 1])
+        bad.append(t)
+    t = good.copy()
+    t[p_nan] = np.nan
+    bad.append(t)
+    want = [p + 1 for p in ps] + [p_nan + 1]
+    half = len(bad) // 2
+    Z = rhs_columns(n, 2)
+    G0, s0, i0 = gm.toeplitz_gram(good, Z, backend=backend)
+    assert i0 == 0
+    G, sld, info = gm.toeplitz_gram(np.stack(bad[:half] + [good] + bad[half:]), Z, backend=backend)
+    assert list(info) == want[:half] + [0] + want[half:], (n, list(info))
+    rest = np.arange(len(info)) != half
+    assert np.isnan(sld[rest]).all() and np.isnan(G[rest]).all()
+    assert np.array_equal(G[half], G0) and sld[half] == s0
+    return [int(x) for x in info]
+
+
+# ---- (g) the host loop over chunks of first columns -----------------------------------------------------------------------------------
+Y_BUDGET = 256 << 20                     # bytes of solved columns in flight (gsum_toep.hip: kYBudget)
+CHUNKED = dict(n=513, c=16, n_sets=2045, m=3)
+
+
+def first_columns_per_launch(n, ncols, m, budget=Y_BUDGET):
+    """The library's arithmetic: how many first columns one launch of the recursion takes."""
+    return max(1, min(m, 65535, budget // (n * ncols * 8)))
+
+
+def check_chunk_loop(backend):
+    """(g): a call whose solved columns exceed the library's budget, so that its three first columns go through one per launch
+    (offsets into t, sum_log_diag, info and G; Y reused).  The middle one fails at step 3.  For each good one, G of the first, middle
+    and last set and sum_log_diag are bitwise those of a call with that column and those three sets alone.  Device only (135 MB of Z)."""
+    n, c, n_sets, m = (CHUNKED[k] for k in ("n", "c", "n_sets", "m"))
+    assert first_columns_per_launch(n, n_sets * c, m) == 1
+    goods = [arfima_column(n, d) for d in DS]
+    bad = goods[0].copy()
+    p = 2
+    bad[p] += 1.5 * float(arfima_energies(n, DS[0])[p - 1])
+    Z = np.asfortranarray(np.random.RandomState(11).standard_normal((n_sets * c, n)).T)
+    G, sld, info = gm.toeplitz_gram(np.stack([goods[0], bad, goods[1]]), Z, n_sets, backend=backend)
+    assert list(info) == [0, p + 1, 0], info
+    assert np.isnan(sld[1]) and np.isnan(G[1]).all()
+    pick = [0, n_sets // 2, n_sets - 1]
+    Z3 = np.concatenate([Z[:, s * c:(s + 1) * c] for s in pick], axis=1)
+    for i, t in ((0, goods[0]), (2, goods[1])):
+        Gs, ss, is_ = gm.toeplitz_gram(t, Z3, 3, backend=backend)
+        assert is_ == 0 and np.array_equal(G[i][pick], Gs) and sld[i] == ss, i
+        assert np.isfinite(G[i]).all()
+    return [int(x) for x in info]
+
+
+# ---- (h) scaling, and the range of the fp32 correction word --------------------------------------------------------------------------
+SCALINGS = ((40, 0), (-40, 0), (0, 20), (0, -20), (30, -15))
+FAR = (140, -140)
+
+
+def check_scaling(backend, name="matern52_n64"):
+    """(h): G(2^a Z, 4^j t) == 2^(2a - 2j) G(Z, t) bit for bit (a power of 4 keeps 1 / sqrt(t_0) exactly scaled) and sum_log_diag moves by
+    n j ln 2 within the floor.  On the golden where the fp32 correction word for the low words of L matters."""
+    t, Z, Gt, st, d_np, d_cpu = _ill_yardsticks(name)
+    n = t.size
+    G0, s0, i0 = gm.toeplitz_gram(t, Z, backend=backend)
+    assert i0 == 0
+    worst = 0.0
+    for a, j in SCALINGS:
+        G, s, info = gm.toeplitz_gram(4.0 ** j * t, 2.0 ** a * Z, backend=backend)
+        assert info == 0
+        assert np.array_equal(G, 2.0 ** (2 * a - 2 * j) * G0), (a, j)
+        want = s0 + n * j * np.log(2.0)
+        worst = max(worst, abs(s - want) / max(1.0, abs(want)))
+        assert abs(s - want) <= FLOOR * max(1.0, abs(want)), (a, j, s, want)
+    return worst
+
+
+def check_far_scaling(backend, a, name="matern52_n64"):
+    """(h): right-hand sides scaled by 2^a with |a| = 140, beyond what an fp32 word holds: finite, info 0, and after scaling back inside
+    the two bounds of (d)."""
+    t, Z, Gt, st, d_np, d_cpu = _ill_yardsticks(name)
+    G, sld, info = gm.toeplitz_gram(t, 2.0 ** a * Z, backend=backend)
+    assert info == 0 and np.isfinite(G).all() and np.isfinite(sld), (a, info)
+    d = distances(G[0] * 2.0 ** (-2 * a), sld, Gt, st)
+    print(f"toeplitz far scaling {backend} a={a}: G {d[0]:.3g} (numpy {d_np[0]:.3g}, cpu {d_cpu[0]:.3g}), sum_log_diag {d[1]:.3g}")
+    for k in range(2):
+        assert d[k] <= max(d_np[k], FLOOR), (a, k, d, d_np)
+        assert d[k] <= 4 * max(d_cpu[k], FLOOR), (a, k, d, d_cpu)
+    return d
 
 
 def notebook_process(g, cls, backend):
