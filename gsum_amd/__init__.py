@@ -23,7 +23,8 @@ from . import refdist
 from .graphical import GraphicalDiagnostic
 from .pointwise import TruncationPointwise
 from .loo import FoldResult, LooResult, kfold_from_factor, loo_from_factor, make_folds
-from .toeplitz import toeplitz_column, toeplitz_gram, uniform_grid_step
+from .toeplitz import (toeplitz_column, toeplitz_grad, toeplitz_gradient_columns, toeplitz_gram, toeplitz_inverse_column, toeplitz_solve,
+                       uniform_grid_step)
 from .stats import hpd, hpd_pdf, median_pdf, cartesian
 from .grid import shard_range, gather_flat, lml_grid_distributed, predict_distributed
 from ._lib import HipContext, HipGroup, KernelDesc, default_context, default_group, device_count, lab_context, load_library
@@ -34,5 +35,6 @@ __all__ = [
     "TruncationGP", "TruncationTP", "posterior_from_gram", "lml_from_gram", "lml_from_gram_batch", "student_lml_from_gram", "cov_factor", "describe_kernel", "describe_thetas", "make_gaussian_partial_sums",
     "make_gaussian_partial_sums_uniform", "make_gaussian_partial_sums_on_grid", "sample_mvn_cholesky", "shard_range", "gather_flat",
     "lml_grid_distributed", "Diagnostic", "pivoted_cholesky", "VariogramFourthRoot", "GraphicalDiagnostic", "refdist",
-    "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "toeplitz_column", "toeplitz_gram", "uniform_grid_step", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
+    "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "toeplitz_column", "toeplitz_gram", "uniform_grid_step", "toeplitz_inverse_column", "toeplitz_solve", "toeplitz_grad",
+    "toeplitz_gradient_columns", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
 ]

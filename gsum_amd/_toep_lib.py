@@ -22,8 +22,13 @@ PROTOTYPES = {
     "gsum_toep_max_n": (C.c_int64, [_p]),
     "gsum_toep_gram": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_toep_grad": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32), _dp,
+                                 _dp]),
+    "gsum_toep_solve": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_grad_times": (C.c_int, [_p, _dp, C.c_int32]),
 }
 PHASES = ("h2d", "schur", "gram", "d2h")
+GRAD_PHASES = ("h2d", "schur", "levinson", "gram", "diagsums", "solve", "contract", "d2h")    # of grad and solve (gsum_toep_grad_times)
 MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
 
 
@@ -71,6 +76,49 @@ class DeviceToeplitz(DeviceHandle):
         with self._lock:
             _check(self._lib, self._lib.gsum_toep_gram(self._handle(), _d(t), m, n, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info)))
         return G, sld, info
+
+    def grad(self, t, dt, Z, n_sets):
+        """(G, sum_log_diag, info, trace (m, P), H (m, n_sets, P, c, c)) of the first columns t (m, n), their derivative columns dt
+        (m, P, n) and the right-hand sides Z (n, n_sets * c): gsum_toep_grad."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        dt = np.ascontiguousarray(dt, dtype=np.float64)
+        Zf = np.asfortranarray(Z, dtype=np.float64)
+        m, n = t.shape
+        P = dt.shape[1]
+        cols = Zf.shape[1] // n_sets
+        G = np.empty((m, n_sets, cols, cols))
+        H = np.empty((m, n_sets, P, cols, cols))
+        trace = np.empty((m, P))
+        sld = np.empty(m)
+        info = np.empty(m, dtype=np.int32)
+        with self._lock:
+            _check(self._lib, self._lib.gsum_toep_grad(self._handle(), _d(t), m, n, _d(dt), P, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info),
+                                                       _d(trace), _d(H)))
+        return G, sld, info, trace, H
+
+    def solve(self, t, Z, want_x=True):
+        """(x (m, n) or None, alpha (m, n, c) or None, info): the first column of the inverse and T^-1 Z (Z None: x alone):
+        gsum_toep_solve."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        m, n = t.shape
+        x = np.empty((m, n)) if want_x else None
+        Zf = alpha = None
+        ncols = 0
+        if Z is not None:
+            Zf = np.asfortranarray(Z, dtype=np.float64)
+            ncols = Zf.shape[1]
+            alpha = np.empty((m, n, ncols))
+        info = np.empty(m, dtype=np.int32)
+        with self._lock:
+            _check(self._lib, self._lib.gsum_toep_solve(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols,
+                                                        None if x is None else _d(x), None if alpha is None else _d(alpha), _i32(info)))
+        return x, alpha, info
+
+    def grad_times(self, reset=False):
+        """Device milliseconds spent so far by ``grad`` and ``solve``, by phase (GRAD_PHASES)."""
+        ms = np.zeros(len(GRAD_PHASES))
+        _check(self._lib, self._lib.gsum_toep_grad_times(self._handle(), _d(ms), int(bool(reset))))
+        return dict(zip(GRAD_PHASES, ms.tolist()))
 
     def times(self, reset=False):
         """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""

@@ -16,8 +16,9 @@
                         diagonal and the blocks of the precision matrix, (L L^T)^-1 R and the predictions of every group of a
                         partition from the points outside it.  Its own small library, built like the variogram's.
 ``libgsum_toep.so``     the Toeplitz likelihood path (include/gsum_toep.h): the Schur recursion of a symmetric Toeplitz matrix in
-                        double-double arithmetic with the forward substitution beside it, and the Gram matrices of the solved
-                        columns.  Its own small library, built like the variogram's.
+                        double-double arithmetic with the forward substitution beside it, the Gram matrices of the solved
+                        columns, and the gradient pieces from the first column of the inverse (Levinson's recursion,
+                        Gohberg-Semencul).  Its own small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations

@@ -280,6 +280,7 @@ class ConjugateGaussianProcess:
         # operator interface on numpy / scipy / scikit-learn (gsum_amd/_cpu.py; BASELINE config 1) -- only when asked for
         self.backend = resolve_backend(backend)
         self.batch_restarts = True   # multi-start fits advance in lock step, objective evaluations batched on the device
+        self._fit_structure = None   # "toeplitz" while fit(structure="toeplitz") calibrates
         self._ctx = None
         self._L_dev = None          # device-resident Cholesky factor of kernel_(X_train_) + nugget
         self._replicas = {}         # ... and its copies on the other devices of predict(devices=...) (id(context) -> factor)
@@ -565,7 +566,15 @@ class ConjugateGaussianProcess:
             raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
         if eval_gradient:
             raise NotImplementedError('structure="toeplitz" has no gradient: tr(T^-1 dT) needs the diagonal sums of T^-1')
-        from .toeplitz import column_of_desc, toeplitz_gram, uniform_grid_step
+        from .toeplitz import toeplitz_gram
+        X, Z, cols, _ = self._structured_inputs(thetas, X, y)
+        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend)
+        vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
+        return np.where(info != 0, -np.inf, vals)                                    # models.py:970-972
+
+    def _structured_inputs(self, thetas, X, y):
+        """(X, Z, the first column of every theta's kernel matrix, the kernel) of ``structure="toeplitz"``, after its checks."""
+        from .toeplitz import column_of_desc, uniform_grid_step
         self._check_decomposition()
         kernel = self._active_kernel()
         X = np.asarray(self.X_train_ if X is None else X, dtype=float)
@@ -580,9 +589,28 @@ class ConjugateGaussianProcess:
         descs = iter(describe_thetas(kernel, given, 1)) if given else iter(())
         ctx = self._context()
         cols = np.stack([column_of_desc(ctx, next(descs) if t is not None else describe_kernel(kernel, 1), X, self.nugget) for t in thetas])
-        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend)
+        return X, Z, cols, kernel
+
+    def _lml_grad_structured(self, structure, thetas, X, y):
+        """``[(lml, grad), ...]`` of ``structure="toeplitz"``: the first column of every theta's kernel matrix and
+        of its derivative by every hyperparameter, one device call for all of them (``toeplitz_grad``), then the host algebra of the
+        dense route.  The values are those of the route without the gradient, bit for bit."""
+        if structure != "toeplitz":
+            raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+        from .toeplitz import toeplitz_grad, toeplitz_gradient_columns
+        X, Z, cols, kernel = self._structured_inputs(thetas, X, y)
+        if kernel.n_dims == 0:
+            return [(float(v), np.zeros(0)) for v in self._lml_structured(structure, thetas, False, X, y)]
+        dts = np.stack([toeplitz_gradient_columns(kernel, X, t) for t in thetas])
+        G, sld, info, trace, H = toeplitz_grad(cols, dts, Z, 1, device=self.device, backend=self.backend)
         vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
-        return np.where(info != 0, -np.inf, vals)                                    # models.py:970-972
+        out = []
+        for i, t in enumerate(thetas):
+            if info[i] != 0:
+                out.append((-np.inf, np.zeros_like(t)))                              # models.py:970-972
+            else:
+                out.append((float(vals[i]), self._lml_grad_gram(G[i, 0], sld[i], trace[i], H[i, 0], X.shape[0])[1]))
+        return out
 
     def _lml_many_curves(self, desc, kernel, theta, eval_gradient, X, y):
         """log_marginal_likelihood for more than GSUM_MAX_RHS - 1 curves: one device call per chunk of curves (see _rhs_chunks)."""
@@ -642,13 +670,17 @@ class ConjugateGaussianProcess:
             raise ValueError("Unknown optimizer %s." % self.optimizer)
         return theta_opt, func_min
 
-    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None):
+    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None, eval_gradient=False):
         """``log_marginal_likelihood(theta, eval_gradient=True)`` for several ``theta`` at once: [(lml, grad), ...].  The
         evaluations are independent and go to the device as one pipelined batch (gsum_lml_grad_batch); every entry equals
         the single call's result bit for bit.  ``structure="toeplitz"``: the values alone, as an array with one entry per theta
-        (``log_marginal_likelihood(theta, structure="toeplitz")``; that route has no gradient), from one device call."""
+        (``log_marginal_likelihood(theta, structure="toeplitz")``), from one device call; with ``eval_gradient=True`` the dense
+        batch's [(lml, grad), ...] from one device call.  ``eval_gradient`` is read on that route alone."""
         if structure is not None:
-            return self._lml_structured(structure, [np.atleast_1d(np.asarray(t, dtype=float)) for t in thetas], False, X, y)
+            thetas = [np.atleast_1d(np.asarray(t, dtype=float)) for t in thetas]
+            if eval_gradient:
+                return self._lml_grad_structured(structure, thetas, X, y)
+            return self._lml_structured(structure, thetas, False, X, y)
         self._check_decomposition()
         base = self._active_kernel()
         X = np.asarray(self.X_train_ if X is None else X, dtype=float)
@@ -684,7 +716,10 @@ class ConjugateGaussianProcess:
         def flush():                       # called with the lock held: every live start has asked
             ids = sorted(pending)
             try:
-                vals = self.log_marginal_likelihood_batch([pending[i] for i in ids])
+                if self._fit_structure is not None:
+                    vals = self.log_marginal_likelihood_batch([pending[i] for i in ids], structure=self._fit_structure, eval_gradient=True)
+                else:
+                    vals = self.log_marginal_likelihood_batch([pending[i] for i in ids])
             except BaseException as exc:   # noqa: BLE001 -- handed to every waiting thread
                 state["error"] = exc
                 vals = [(np.nan, None)] * len(ids)
@@ -755,6 +790,11 @@ class ConjugateGaussianProcess:
         initial points are drawn in the reference's order, so the starts -- and the optima -- are the sequential loop's."""
         if self.optimizer is not None and self.kernel_.n_dims > 0:
             def obj_func(theta, eval_gradient=True):                                   # models.py:634-640
+                if self._fit_structure is not None:                                   # the structured route: the batch of one
+                    if eval_gradient:
+                        lml, grad = self.log_marginal_likelihood_batch([theta], structure=self._fit_structure, eval_gradient=True)[0]
+                        return -lml, -grad
+                    return -float(self.log_marginal_likelihood_batch([theta], structure=self._fit_structure)[0])
                 if eval_gradient:
                     lml, grad = self.log_marginal_likelihood(theta, eval_gradient=True)
                     return -lml, -grad
@@ -778,8 +818,31 @@ class ConjugateGaussianProcess:
             return -float(values[best])
         return None
 
-    def fit(self, X, y):
+    def fit(self, X, y, structure=None):
+        """``structure="toeplitz"``: every objective evaluation of the calibration -- the single start's and the lock-step restarts' --
+        runs on the structured route (``log_marginal_likelihood_batch(.., structure="toeplitz", eval_gradient=True)``); X must be a
+        uniform one-dimensional grid and the kernel stationary, checked before the optimiser starts.  The final factorisation, the
+        posterior and ``predict`` stay dense."""
         self._check_decomposition()
+        if structure is not None:
+            if structure != "toeplitz":
+                raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+            from .toeplitz import _is_stationary, uniform_grid_step
+            Xs = np.asarray(X, dtype=float)
+            if Xs.ndim != 2 or Xs.shape[1] != 1:
+                raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: X must have shape (n, 1), got {Xs.shape}')
+            uniform_grid_step(Xs)
+            if not _is_stationary(describe_kernel(self._default_kernel if self.kernel is None else self.kernel, 1)):
+                raise NotImplementedError("the Toeplitz path needs a stationary kernel: this one has a DotProduct leaf")
+            if self._many_curves(y):
+                raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
+        self._fit_structure = structure
+        try:
+            return self._fit_dense_after_calibration(X, y)
+        finally:
+            self._fit_structure = None
+
+    def _fit_dense_after_calibration(self, X, y):
         self.kernel_ = clone(self._default_kernel if self.kernel is None else self.kernel)   # models.py:685-688
         self._rng = check_random_state(self.random_state)
         if self.copy_X_train:

@@ -15,6 +15,8 @@ static_assert(gt::kMaxN == GSUM_TOEP_MAX_N && gt::kMaxCols == GSUM_TOEP_MAX_COLS
 namespace {
 
 enum Phase { kH2D = 0, kSchur, kGram, kD2H, kPhases };
+// the phases of gsum_toep_grad and gsum_toep_solve (gsum_toep_grad_times), after those of gsum_toep_gram in one array
+enum GradPhase { kGH2D = kPhases, kGSchur, kGLevinson, kGGram, kGDiag, kGSolve, kGContract, kGD2H, kAllPhases };
 
 constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y) in flight: the first columns go through in chunks
 
@@ -23,7 +25,8 @@ constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y
 struct gsum_toep : Handle {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
-    double ms[kPhases] = {0, 0, 0, 0};
+    DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
+    double ms[kAllPhases] = {};
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
     ~gsum_toep() {
         for (auto& e : pending) {
@@ -37,7 +40,7 @@ namespace {
 
 // Run f (enqueues on h->stream) between two events charged to a phase; settle() turns them into milliseconds after the sync.
 template <class F>
-void timed(gsum_toep* h, Phase ph, F&& f) {
+void timed(gsum_toep* h, int ph, F&& f) {
     hipEvent_t a = nullptr, b = nullptr;
     SL_CHECK(hipEventCreate(&a));
     if (hipEventCreate(&b) != hipSuccess) {
@@ -87,14 +90,74 @@ void launch_schur(gsum_toep* h, const double* t, int n, int ncols, int64_t m, do
     const dim3 grid((unsigned)((ncols + C - 1) / C), (unsigned)m);
     hipStream_t st = h->stream;
     if (n <= gt::kThreads)
-        gt::k_schur<1, 16, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
+        gt::k_schur<1, 16, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
     else if (n <= 4 * gt::kThreads)
-        gt::k_schur<4, 12, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
+        gt::k_schur<4, 12, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
     else if (n <= 8 * gt::kThreads)
-        gt::k_schur<8, 5, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
+        gt::k_schur<8, 5, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
     else
-        gt::k_schur<16, 3, true><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info);
+        gt::k_schur<16, 3, true, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
     SL_LAUNCHED("k_schur");
+}
+
+// The same recursion handing out its reflection coefficients and rotations (steps, (m, n, 4)), then the one that replays them into
+// x = T^-1 e_0 (xd both words, xf rounded).  Z / ze are the columns the forward substitution runs on.
+void launch_schur_steps(gsum_toep* h, const double* t, int n, const double* Z, const int32_t* ze, int ncols, int64_t m, double* Y,
+                        double* sld, int32_t* info, double* steps) {
+    // handing out the coefficients costs a few registers, which the value path's classes do not have to spare: fewer columns per
+    // chunk here (a column's solved values do not depend on its chunk)
+    const int C = chunk_cols(n);
+    const dim3 grid((unsigned)((ncols + C - 1) / C), (unsigned)m);
+    hipStream_t st = h->stream;
+    if (n <= gt::kThreads)
+        gt::k_schur<1, 16, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
+    else if (n <= 4 * gt::kThreads)
+        gt::k_schur<4, 12, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
+    else if (n <= 8 * gt::kThreads)
+        gt::k_schur<8, 5, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
+    else
+        gt::k_schur<16, 3, true, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
+    SL_LAUNCHED("k_schur");
+}
+
+void launch_levinson(gsum_toep* h, const double* t, int n, int64_t m, double* steps, double* xd, double* xf, double* sld, int32_t* info) {
+    hipStream_t st = h->stream;
+    gt::k_coeffs<<<dim3((unsigned)((n + 255) / 256), (unsigned)m), 256, 0, st>>>(steps, n, info);
+    SL_LAUNCHED("k_coeffs");
+    if (n <= gt::kThreads)
+        gt::k_levinson<1><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
+    else if (n <= 4 * gt::kThreads)
+        gt::k_levinson<4><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
+    else if (n <= 8 * gt::kThreads)
+        gt::k_levinson<8><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
+    else
+        gt::k_levinson<16><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
+    SL_LAUNCHED("k_levinson");
+}
+
+// What gsum_toep_gram refuses about the first columns, for the entry point `who`.
+void check_first_columns(const char* who, const double* t, int64_t m, int64_t n) {
+    if (m < 1 || n < 1) throw Error(std::string(who) + ": m and n must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n));
+    if (n > gt::kMaxN)
+        throw Error(std::string(who) + ": n must be <= " + std::to_string(gt::kMaxN) + " (one workgroup holds the generator), got " + std::to_string(n));
+    for (int64_t i = 0; i < m; ++i) {
+        const double t0 = t[i * n];
+        if (t0 > 0.0 && t0 < INFINITY && (t0 < 0x1p-64 || t0 > 0x1p64)) {
+            char got[32];
+            snprintf(got, sizeof got, "%g", t0);
+            throw Error(std::string(who) + ": t[0] must lie within 2^-64 .. 2^64 (scale t by a power of 4), got " + std::string(got) +
+                        " in first column " + std::to_string(i));
+        }
+    }
+}
+
+// alpha of cnt first columns from their xd: As (scaled columns) and, if not null, alpha_out (cnt, n, ncols).
+void launch_solve(gsum_toep* h, int n, int ncols, int64_t cnt, const double* xd, const int32_t* info, double* alpha_out) {
+    const dim3 grid((unsigned)(n * ncols), (unsigned)cnt);
+    gt::k_gs_first<<<grid, gt::kWave, 0, h->stream>>>(xd, n, h->Z.p, h->ze.p, ncols, info, h->W.p);
+    SL_LAUNCHED("k_gs_first");
+    gt::k_gs_second<<<grid, gt::kWave, 0, h->stream>>>(xd, n, h->W.p, h->ze.p, ncols, info, h->As.p, alpha_out);
+    SL_LAUNCHED("k_gs_second");
 }
 
 }  // namespace
@@ -180,6 +243,163 @@ GT_API int gsum_toep_times(gsum_toep* h, double* ms, int32_t reset) {
         if (!h || !ms) throw Error("gsum_toep_times: null pointer argument");
         for (int k = 0; k < kPhases; ++k) {
             ms[k] = h->ms[k];
+            if (reset) h->ms[k] = 0;
+        }
+    });
+}
+
+GT_API int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z, int64_t n_sets,
+                          int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out) {
+    return guarded([&] {
+        if (!h || !t || !dt || !Z || !G_out || !sld_out || !info_out || !trace_out || !H_out) throw Error("gsum_toep_grad: null pointer argument");
+        if (n_sets < 1) throw Error("gsum_toep_grad: n_sets must be >= 1, got " + std::to_string(n_sets));
+        if (P < 1 || P > 65535) throw Error("gsum_toep_grad: P must be between 1 and 65535, got " + std::to_string(P));
+        if (cols < 1 || cols > gt::kMaxCols)
+            throw Error("gsum_toep_grad: cols must be between 1 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(cols));
+        check_first_columns("gsum_toep_grad", t, m, n);
+        if (n_sets > 65535) throw Error("gsum_toep_grad: n_sets must be <= 65535, got " + std::to_string(n_sets));
+        if (n_sets * cols > (((int64_t)1 << 31) - 1) / n)
+            throw Error("gsum_toep_grad: n * n_sets * cols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(n_sets) + " x " + std::to_string(cols));
+        if ((int64_t)cols * cols * P > ((int64_t)1 << 31) - 1) throw Error("gsum_toep_grad: cols * cols * P must be < 2^31");
+        const int ncols = (int)(n_sets * cols);
+        const size_t per_theta = (size_t)n * ncols;                            // doubles of Y, and of alpha, per first column
+        const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (2 * per_theta * sizeof(double)))));
+        const size_t gsz = (size_t)n_sets * cols * cols, hsz = gsz * (size_t)P;
+        run(h, [&] {
+            h->t.reserve((size_t)m * n);
+            h->dt.reserve((size_t)m * P * n);
+            h->Z.reserve(per_theta);
+            h->Y.reserve(per_theta * step);
+            h->As.reserve(per_theta * step);
+            h->W.reserve(4 * per_theta * step);
+            h->Q.reserve(2 * per_theta * step * P);
+            h->steps.reserve((size_t)4 * n * step);
+            h->xd.reserve((size_t)2 * n * step);
+            h->xf.reserve((size_t)n * step);
+            h->sd.reserve((size_t)2 * n * step);
+            h->G.reserve(gsz * m);
+            h->H.reserve(hsz * m);
+            h->trace.reserve((size_t)m * P);
+            h->sld.reserve((size_t)m);
+            h->info.reserve((size_t)m);
+            h->ze.reserve((size_t)ncols);
+            hipStream_t st = h->stream;
+            timed(h, kGH2D, [&] {
+                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->dt.p, dt, sizeof(double) * m * P * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
+            });
+            timed(h, kGSchur, [&] {
+                gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
+                SL_LAUNCHED("k_colexp");
+            });
+            for (int64_t lo = 0; lo < m; lo += step) {
+                const int64_t cnt = std::min(step, m - lo);
+                const double* tl = h->t.p + lo * n;
+                int32_t* il = h->info.p + lo;
+                timed(h, kGSchur, [&] { launch_schur_steps(h, tl, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p, h->sld.p + lo, il); });
+                timed(h, kGGram, [&] {
+                    gt::k_gram<<<dim3((unsigned)cols, (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(h->Y.p, (int)n, cols, (int)n_sets,
+                                                                                                         h->ze.p, il, h->G.p + gsz * lo);
+                    SL_LAUNCHED("k_gram");
+                });
+                timed(h, kGDiag, [&] {
+                    gt::k_diagsums<<<dim3((unsigned)n, (unsigned)cnt), gt::kWave, 0, st>>>(h->xd.p, (int)n, il, h->sd.p);
+                    SL_LAUNCHED("k_diagsums");
+                    gt::k_traces<<<dim3((unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->sd.p, h->dt.p + lo * P * n, (int)n, (int)P, il,
+                                                                                         h->trace.p + lo * P);
+                    SL_LAUNCHED("k_traces");
+                });
+                timed(h, kGSolve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, nullptr); });
+                timed(h, kGContract, [&] {
+                    gt::k_tprod<<<dim3((unsigned)(n * ncols), (unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->dt.p + lo * P * n, (int)n, (int)P,
+                                                                                                            h->As.p, ncols, il, h->Q.p);
+                    SL_LAUNCHED("k_tprod");
+                    gt::k_hdot<<<dim3((unsigned)(cols * cols * P), (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(
+                        h->As.p, h->Q.p, (int)n, (int)P, cols, (int)n_sets, h->ze.p, il, h->H.p + hsz * lo);
+                    SL_LAUNCHED("k_hdot");
+                });
+            }
+            timed(h, kGD2H, [&] {
+                SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * gsz * m, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(H_out, h->H.p, sizeof(double) * hsz * m, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(trace_out, h->trace.p, sizeof(double) * m * P, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+            });
+        });
+    });
+}
+
+GT_API int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols64, double* x_out,
+                           double* alpha_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !info_out || (!x_out && !alpha_out) || (alpha_out && !Z)) throw Error("gsum_toep_solve: null pointer argument");
+        if (alpha_out && ncols64 < 1) throw Error("gsum_toep_solve: ncols must be >= 1, got " + std::to_string(ncols64));
+        check_first_columns("gsum_toep_solve", t, m, n);
+        const int64_t nc = alpha_out ? ncols64 : 0;
+        if (nc > (((int64_t)1 << 31) - 1) / n)
+            throw Error("gsum_toep_solve: n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
+        const int ncols = (int)nc;
+        const size_t per_theta = (size_t)n * std::max(ncols, 1);
+        const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (2 * per_theta * sizeof(double)))));
+        run(h, [&] {
+            h->t.reserve((size_t)m * n);
+            h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
+            h->ze.reserve((size_t)ncols + 1);
+            h->Y.reserve((size_t)n * step);
+            h->steps.reserve((size_t)4 * n * step);
+            h->xd.reserve((size_t)2 * n * step);
+            h->xf.reserve((size_t)n * m);
+            h->sld.reserve((size_t)m);
+            h->info.reserve((size_t)m);
+            if (ncols) {
+                h->As.reserve(per_theta * step);
+                h->Aout.reserve(per_theta * step);
+                h->W.reserve(4 * per_theta * step);
+            }
+            hipStream_t st = h->stream;
+            // the recursion needs no right-hand side here: it runs on one column of zeros, kept after the ncols of Z
+            double* zero = h->Z.p + (size_t)n * ncols;
+            int32_t* zero_e = h->ze.p + ncols;
+            timed(h, kGH2D, [&] {
+                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+                if (ncols) SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * n * ncols, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
+                SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
+            });
+            if (ncols)
+                timed(h, kGSchur, [&] {
+                    gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
+                    SL_LAUNCHED("k_colexp");
+                });
+            for (int64_t lo = 0; lo < m; lo += step) {
+                const int64_t cnt = std::min(step, m - lo);
+                const double* tl = h->t.p + lo * n;
+                int32_t* il = h->info.p + lo;
+                timed(h, kGSchur, [&] { launch_schur_steps(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
+                if (ncols) {
+                    timed(h, kGSolve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
+                    timed(h, kGD2H, [&] {
+                        SL_CHECK(hipMemcpyAsync(alpha_out + (size_t)lo * per_theta, h->Aout.p, sizeof(double) * per_theta * cnt, hipMemcpyDeviceToHost, st));
+                    });
+                }
+            }
+            timed(h, kGD2H, [&] {
+                if (x_out) SL_CHECK(hipMemcpyAsync(x_out, h->xf.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+            });
+        });
+    });
+}
+
+GT_API int gsum_toep_grad_times(gsum_toep* h, double* ms, int32_t reset) {
+    return guarded([&] {
+        if (!h || !ms) throw Error("gsum_toep_grad_times: null pointer argument");
+        for (int k = kPhases; k < kAllPhases; ++k) {
+            ms[k - kPhases] = h->ms[k];
             if (reset) h->ms[k] = 0;
         }
     });

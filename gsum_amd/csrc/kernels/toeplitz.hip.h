@@ -1,7 +1,7 @@
 // Kernels of libgsum_toep.so (gfx950 only): the Schur (Bareiss) recursion of a symmetric positive definite Toeplitz matrix T with a
 // forward substitution beside it, and the Gram matrices of the solved columns.  DESIGN.md section 18.
 //
-// k_schur<E, C, VL>: one workgroup per (first column t, chunk of C right-hand-side columns).  The generator pair (u, v) of T = L L^T is
+// k_schur<E, C, VL, R>: one workgroup per (first column t, chunk of C right-hand-side columns).  The generator pair (u, v) of T = L L^T is
 //   held in double-double (two fp64 words, error-free transformations in plain C++) in registers, E consecutive elements per thread in
 //   the fixed frame: at step k, u[i] = L[i, k] for i >= k.  A step publishes the pivot pair through LDS (one barrier per step, two
 //   buffers), forms rho = v[k+1] / u[k] and 1 / sqrt((1 - rho)(1 + rho)) in every thread, shifts u down by one element (register
@@ -20,6 +20,9 @@
 //   itself).  A column of zeros, or with an infinite entry, is taken as it is.
 // k_gram: G[a, b] = sum_k Y[k, a] Y[k, b] of one set of columns, one wave per (first column, set, a): lane l sums the rows l, l + 64,
 //   ... in order, then a butterfly over the lanes.  The order depends on n alone.
+// The gradient pieces (the comments stand at the kernels): k_schur<.., R = true> hands out the pivot pair of every
+//   step, k_coeffs turns them into (rho, 1 / c), k_levinson<E> replays those into x = T^-1 e_0 in double-double, k_diagsums / k_traces
+//   give tr(T^-1 dT_p), k_gs_first / k_gs_second alpha = T^-1 Z by Gohberg-Semencul, k_tprod / k_hdot alpha^T dT_p alpha.
 // Every value is written with ordinary vector stores; there are no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -104,10 +107,13 @@ __global__ __launch_bounds__(kWave) void k_colexp(const double* __restrict__ Z, 
 // Y is (m, n, ncols) row-major; Z is column-major n x ncols, ze its column exponents (k_colexp); t is (m, n).  grid = (chunks, m),
 // block = kThreads.  Y holds the solved columns of the scaled Z.
 // LDS: pub[buffer] = {u[k].h, u[k].l, v[k+1].h, v[k+1].l, z[k][0..C)}, edge[buffer][thread] = the thread's last u element.
-template <int E, int C, bool VL>
+// R (the gradient path): chunk 0 of a first column also hands out the pivot pair it publishes, steps (m, n, 4): row k = {u[k].h,
+// u[k].l, v[k+1].h, v[k+1].l}, straight from LDS (four threads, a word each), so the step itself holds no more registers than the
+// value path's; k_coeffs turns the rows into (rho, 1 / c).  Without R the kernel is the value path's.
+template <int E, int C, bool VL, bool R>
 __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t, int n, const double* __restrict__ Z,
                                                      const int32_t* __restrict__ ze, int ncols, double* __restrict__ Y,
-                                                     double* __restrict__ sld, int32_t* __restrict__ info) {
+                                                     double* __restrict__ sld, int32_t* __restrict__ info, double* __restrict__ steps) {
     __shared__ double s_pub[2][4 + C];
     __shared__ double s_edge[2][kThreads][2];
     __shared__ alignas(16) double s_v[VL ? E : 1][VL ? kThreads : 1][2];      // VL: v lives here, element e of thread tid at [e][tid]
@@ -173,6 +179,9 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
             yf[c] = (float)y[c];
         }
         if (tid < nc) Yt[(int64_t)k * ncols + col0 + tid] = s_pub[b][4 + tid] * inv;
+        if constexpr (R) {
+            if (tid < 4 && blockIdx.x == 0) steps[(theta * n + k) * 4 + tid] = s_pub[b][tid];
+        }
         if (k == n - 1) break;
         const dd rho = dd_div(dd{s_pub[b][2], s_pub[b][3]}, pu);
         if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every thread
@@ -267,6 +276,271 @@ __global__ __launch_bounds__(kWave) void k_gram(const double* __restrict__ Y, in
         for (int off = 1; off < kWave; off <<= 1) x += __shfl_xor(x, off, kWave);
         if (lane == 0 && bcol < cols) g[bcol] = ldexp(x, ze[set * cols + a] + ze[set * cols + bcol]);
     }
+}
+
+// ---- the gradient pieces ---------------------------------------------------------------------------------------
+// Everything below works from x = T^-1 e_0 (Gohberg-Semencul).  Sums run in double-double in an order fixed by n alone: lane l of a wave
+// takes the terms l, l + 64, ... in order, then the lanes are folded 32, 16, ... 1 onto lane 0.
+
+__device__ __forceinline__ dd wave_fold(dd a) {
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) a = dd_add(a, dd{__shfl_down(a.h, off, kWave), __shfl_down(a.l, off, kWave)});
+    return a;                                                                 // the sum is lane 0's
+}
+__device__ __forceinline__ bool dd_finite(dd a) { return fabs(a.h) < INFINITY && fabs(a.l) < INFINITY; }
+
+// steps row k < n - 1: {u[k], v[k+1]} -> {rho, 1 / c} by the expressions of k_schur's step, so the words are the ones the generator
+// was rotated with; row n - 1 keeps u[n-1] = L[n-1, n-1].  Independent rows: no serial chain.  grid = (ceil(n / 256), m), block = 256.
+__global__ __launch_bounds__(256) void k_coeffs(double* __restrict__ steps, int n, const int32_t* __restrict__ info) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    if (k >= n - 1 || info[theta] != 0) return;
+    double* st = steps + (theta * n + k) * 4;
+    const dd rho = dd_div(dd{st[2], st[3]}, dd{st[0], st[1]});
+    const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
+    st[0] = rho.h;
+    st[1] = rho.l;
+    st[2] = ic.h;
+    st[3] = ic.l;
+}
+
+// Levinson's recursion in its normalised form, replaying the (rho, 1 / c) of k_schur<.., R = true> and k_coeffs: A = B = e_0 / sqrt(t_0), then for
+// k = 1 .. n - 1  A <- (A - rho_k shift(B)) / c_k, B <- (shift(B) - rho_k A) / c_k (shift: down by one), and x = A / L[n-1, n-1].  A
+// and B in double-double in registers, E consecutive elements per thread as in k_schur; B's element that crosses a thread boundary
+// goes through edge[buffer][thread], one barrier per step.  The coefficients of the next step are loaded a step ahead.  grid = m,
+// block = kThreads.  xd is (m, n, 2) (both words), xf (m, n) its fp64 rounding; a first column with info != 0 gives NaN; one whose x
+// is not finite gets info = n + 1 and a NaN sld.
+template <int E>
+__global__ __launch_bounds__(kThreads) void k_levinson(const double* __restrict__ t, int n, const double* __restrict__ steps,
+                                                        double* __restrict__ xd, double* __restrict__ xf, double* __restrict__ sld,
+                                                        int32_t* __restrict__ info) {
+    __shared__ double s_edge[2][kThreads][2];
+    const int tid = threadIdx.x, base = tid * E;
+    const int64_t theta = blockIdx.x;
+    const double* st = steps + theta * n * 4;
+    double* xo = xd + theta * n * 2;
+    double* xr = xf + theta * n;
+    if (info[theta] != 0) {                                                   // the same in every thread
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (base + e < n) xo[2 * (base + e)] = xo[2 * (base + e) + 1] = xr[base + e] = NAN;
+        return;
+    }
+    double ah[E], al[E], bh[E], bl[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) ah[e] = al[e] = bh[e] = bl[e] = 0.0;
+    if (tid == 0) {
+        const dd rs = dd_rsqrt(dd{t[theta * n], 0.0});
+        ah[0] = bh[0] = rs.h;
+        al[0] = bl[0] = rs.l;
+    }
+    s_edge[0][tid][0] = bh[E - 1];
+    s_edge[0][tid][1] = bl[E - 1];
+    s_edge[1][tid][0] = s_edge[1][tid][1] = 0.0;
+    double c0 = 0.0, c1 = 0.0, c2 = 1.0, c3 = 0.0;                            // the coefficients of the coming step
+    if (n > 1) {
+        c0 = st[0];
+        c1 = st[1];
+        c2 = st[2];
+        c3 = st[3];
+    }
+    __syncthreads();
+    for (int k = 1; k < n; ++k) {
+        const int b = (k - 1) & 1, nb = b ^ 1;
+        const dd nrho = {-c0, -c1}, ic = {c2, c3};
+        if (k + 1 < n) {                                                      // step k + 1 replays row k
+            const double* nx = st + (int64_t)k * 4;
+            c0 = nx[0];
+            c1 = nx[1];
+            c2 = nx[2];
+            c3 = nx[3];
+        }
+        if (base <= k) {                                                      // elements beyond k are still zero
+            dd edge = {0.0, 0.0};
+            if (tid > 0) edge = {s_edge[b][tid - 1][0], s_edge[b][tid - 1][1]};
+#pragma unroll
+            for (int e = E - 1; e >= 0; --e) {
+                const dd bs = e > 0 ? dd{bh[e > 0 ? e - 1 : 0], bl[e > 0 ? e - 1 : 0]} : edge;       // B shifted down by one
+                const dd a = {ah[e], al[e]};
+                const dd an = dd_mul(dd_add(a, dd_mul(nrho, bs)), ic);
+                const dd bn = dd_mul(dd_add(bs, dd_mul(nrho, a)), ic);
+                ah[e] = an.h;
+                al[e] = an.l;
+                bh[e] = bn.h;
+                bl[e] = bn.l;
+            }
+            s_edge[nb][tid][0] = bh[E - 1];
+            s_edge[nb][tid][1] = bl[E - 1];
+        }
+        __syncthreads();
+    }
+    const dd last = {st[(int64_t)(n - 1) * 4], st[(int64_t)(n - 1) * 4 + 1]};
+    int notfinite = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const dd x = dd_div(dd{ah[e], al[e]}, last);
+        ah[e] = x.h;
+        al[e] = x.l;
+        if (base + e < n && !dd_finite(x)) notfinite = 1;
+    }
+    notfinite = __syncthreads_or(notfinite);
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = base + e;
+        if (i < n) {
+            xo[2 * i] = notfinite ? NAN : ah[e];
+            xo[2 * i + 1] = notfinite ? NAN : al[e];
+            xr[i] = notfinite ? NAN : ah[e];
+        }
+    }
+    if (notfinite && tid == 0) {
+        info[theta] = n + 1;
+        sld[theta] = NAN;
+    }
+}
+
+// sd[theta, d] = the sum of the d-th diagonal of T^-1 = (1 / x_0) sum_{m <= n-1-d} (n - d - 2 m) x_m x_{m+d}, both words.  The weight is
+// an integer below 2^14 in magnitude: exact.  grid = (n, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_diagsums(const double* __restrict__ xd, int n, const int32_t* __restrict__ info,
+                                                     double* __restrict__ sd) {
+    const int d = blockIdx.x, lane = threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    double* out = sd + (theta * n + d) * 2;
+    if (info[theta] != 0) {
+        if (lane == 0) out[0] = out[1] = NAN;
+        return;
+    }
+    const double* x = xd + theta * n * 2;
+    dd acc = {0.0, 0.0};
+    for (int m = lane; m <= n - 1 - d; m += kWave) {
+        const dd p = dd_mul(dd{x[2 * m], x[2 * m + 1]}, dd{x[2 * (m + d)], x[2 * (m + d) + 1]});
+        acc = dd_add(acc, dd_mul_d(p, (double)(n - d - 2 * m)));
+    }
+    acc = wave_fold(acc);
+    if (lane == 0) {
+        const dd s = dd_div(acc, dd{x[0], x[1]});
+        out[0] = s.h;
+        out[1] = s.l;
+    }
+}
+
+// trace[theta, p] = dt_p[0] s_0 + 2 sum_{d >= 1} dt_p[d] s_d.  dt is (m, P, n).  grid = (P, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_traces(const double* __restrict__ sd, const double* __restrict__ dt, int n, int P,
+                                                   const int32_t* __restrict__ info, double* __restrict__ trace) {
+    const int p = blockIdx.x, lane = threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    if (info[theta] != 0) {
+        if (lane == 0) trace[theta * P + p] = NAN;
+        return;
+    }
+    const double* s = sd + theta * n * 2;
+    const double* d = dt + (theta * P + p) * n;
+    dd acc = {0.0, 0.0};
+    for (int k = lane; k < n; k += kWave) acc = dd_add(acc, dd_mul_d(dd{s[2 * k], s[2 * k + 1]}, k ? 2.0 * d[k] : d[k]));
+    acc = wave_fold(acc);
+    if (lane == 0) trace[theta * P + p] = acc.h;
+}
+
+// The first half of alpha = T^-1 z = (1 / x_0) [L(x) L(x)^T - L(xt) L(xt)^T] z, L(.) the lower-triangular Toeplitz matrix of a first
+// column and xt = (0, x_{n-1}, .., x_1):  W[theta, col, j] = {w1.h, w1.l, w2.h, w2.l},  w1[j] = sum_{r <= n-1-j} x_r z_{j+r},
+// w2[j] = sum_{1 <= r <= n-1-j} x_{n-r} z_{j+r}.  z is loaded scaled by 2^-ze[col] as in k_schur.  Z is column-major n x ncols.
+// grid = (n * ncols, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_gs_first(const double* __restrict__ xd, int n, const double* __restrict__ Z,
+                                                     const int32_t* __restrict__ ze, int ncols, const int32_t* __restrict__ info,
+                                                     double* __restrict__ W) {
+    const int col = blockIdx.x / n, j = blockIdx.x % n, lane = threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    if (info[theta] != 0) return;                                             // k_gs_second writes the NaN
+    const double* x = xd + theta * n * 2;
+    const double* z = Z + (int64_t)col * n + j;
+    const int sh = -ze[col];
+    dd a1 = {0.0, 0.0}, a2 = {0.0, 0.0};
+    for (int r = lane; r <= n - 1 - j; r += kWave) {
+        const double zz = ldexp(z[r], sh);
+        a1 = dd_add(a1, dd_mul_d(dd{x[2 * r], x[2 * r + 1]}, zz));
+        if (r > 0) a2 = dd_add(a2, dd_mul_d(dd{x[2 * (n - r)], x[2 * (n - r) + 1]}, zz));
+    }
+    a1 = wave_fold(a1);
+    a2 = wave_fold(a2);
+    if (lane == 0) {
+        double* w = W + ((theta * ncols + col) * n + j) * 4;
+        w[0] = a1.h;
+        w[1] = a1.l;
+        w[2] = a2.h;
+        w[3] = a2.l;
+    }
+}
+
+// The second half: alpha[i] = (sum_{j <= i} x_{i-j} w1[j] - sum_{j < i} x_{n-i+j} w2[j]) / x_0, rounded to fp64.  As (m, ncols, n) keeps
+// alpha of the scaled columns for the contraction; alpha_out (m, n, ncols), if not null, is scaled back by 2^ze[col] (exact).
+// grid = (n * ncols, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_gs_second(const double* __restrict__ xd, int n, const double* __restrict__ W,
+                                                      const int32_t* __restrict__ ze, int ncols, const int32_t* __restrict__ info,
+                                                      double* __restrict__ As, double* __restrict__ alpha_out) {
+    const int col = blockIdx.x / n, i = blockIdx.x % n, lane = threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    double* as = As + (theta * ncols + col) * n + i;
+    double* ao = alpha_out ? alpha_out + (theta * n + i) * ncols + col : nullptr;
+    if (info[theta] != 0) {
+        if (lane == 0) {
+            *as = NAN;
+            if (ao) *ao = NAN;
+        }
+        return;
+    }
+    const double* x = xd + theta * n * 2;
+    const double* w = W + (theta * ncols + col) * n * 4;
+    dd acc = {0.0, 0.0};
+    for (int j = lane; j <= i; j += kWave) {
+        acc = dd_add(acc, dd_mul(dd{x[2 * (i - j)], x[2 * (i - j) + 1]}, dd{w[4 * j], w[4 * j + 1]}));
+        if (j < i) acc = dd_sub(acc, dd_mul(dd{x[2 * (n - i + j)], x[2 * (n - i + j) + 1]}, dd{w[4 * j + 2], w[4 * j + 3]}));
+    }
+    acc = wave_fold(acc);
+    if (lane == 0) {
+        const double a = dd_div(acc, dd{x[0], x[1]}).h;
+        *as = a;
+        if (ao) *ao = ldexp(a, ze[col]);
+    }
+}
+
+// Q[theta, p, col, i] = (dT_p alpha_col)[i] = sum_j dt_p[|i - j|] alpha_col[j], both words.  grid = (n * ncols, P, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_tprod(const double* __restrict__ dt, int n, int P, const double* __restrict__ As, int ncols,
+                                                  const int32_t* __restrict__ info, double* __restrict__ Q) {
+    const int col = blockIdx.x / n, i = blockIdx.x % n, p = blockIdx.y, lane = threadIdx.x;
+    const int64_t theta = blockIdx.z;
+    if (info[theta] != 0) return;                                             // k_hdot writes the NaN
+    const double* d = dt + (theta * P + p) * n;
+    const double* a = As + (theta * ncols + col) * n;
+    dd acc = {0.0, 0.0};
+    for (int j = lane; j < n; j += kWave) acc = dd_add(acc, two_prod(d[j > i ? j - i : i - j], a[j]));
+    acc = wave_fold(acc);
+    if (lane == 0) {
+        double* q = Q + (((theta * P + p) * ncols + col) * n + i) * 2;
+        q[0] = acc.h;
+        q[1] = acc.l;
+    }
+}
+
+// H[theta, set, p, a, b] = alpha_a^T (dT_p alpha_b) for a <= b, mirrored, scaled back by the two column exponents.
+// grid = (cols * cols * P, n_sets, m), block = kWave.
+__global__ __launch_bounds__(kWave) void k_hdot(const double* __restrict__ As, const double* __restrict__ Q, int n, int P, int cols,
+                                                 int n_sets, const int32_t* __restrict__ ze, const int32_t* __restrict__ info,
+                                                 double* __restrict__ H) {
+    const int b = blockIdx.x % cols, a = (blockIdx.x / cols) % cols, p = blockIdx.x / (cols * cols), set = blockIdx.y, lane = threadIdx.x;
+    const int64_t theta = blockIdx.z;
+    if (a > b) return;
+    const int ncols = n_sets * cols;
+    double* h = H + ((theta * n_sets + set) * P + p) * (int64_t)cols * cols;
+    if (info[theta] != 0) {
+        if (lane == 0) h[a * cols + b] = h[b * cols + a] = NAN;
+        return;
+    }
+    const double* al = As + (theta * ncols + set * cols + a) * n;
+    const double* q = Q + ((theta * P + p) * ncols + set * cols + b) * n * 2;
+    dd acc = {0.0, 0.0};
+    for (int i = lane; i < n; i += kWave) acc = dd_add(acc, dd_mul_d(dd{q[2 * i], q[2 * i + 1]}, al[i]));
+    acc = wave_fold(acc);
+    if (lane == 0) h[a * cols + b] = h[b * cols + a] = ldexp(acc.h, ze[set * cols + a] + ze[set * cols + b]);
 }
 
 }  // namespace gt

@@ -18,7 +18,8 @@ from ._backend import resolve_backend, resolve_device
 from ._lib import FAMILY, GSUM_MAX_RHS, KernelDesc
 from .kernels import describe_kernel
 
-__all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n"]
+__all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n", "toeplitz_inverse_column", "toeplitz_solve",
+           "toeplitz_grad", "toeplitz_gradient_columns"]
 
 
 def uniform_grid_step(X, tol=4.0):
@@ -93,8 +94,10 @@ def toeplitz_max_n(backend=None):
     return _toep_lib.max_n()
 
 
-def _cpu_gram(t, Z, n_sets):
-    """The device's recursion in numpy: the generator in ``numpy.longdouble``, forward substitution and Gram matrices in fp64."""
+def _cpu_gram(t, Z, n_sets, steps=None):
+    """The device's recursion in numpy: the generator in ``numpy.longdouble``, forward substitution and Gram matrices in fp64.
+    ``steps``: a dict that receives what the recursion for the inverse's first column needs (``_cpu_inverse_column``): the reflection
+    coefficients ``rho`` and the rotations' ``1 / c`` (m, n - 1) and the last pivot ``L[n-1, n-1]`` (m,), all in long double."""
     ld = np.longdouble
     m, n = t.shape
     cols = Z.shape[1] // n_sets
@@ -111,6 +114,8 @@ def _cpu_gram(t, Z, n_sets):
         Y = np.zeros_like(R)
         sld = np.zeros(m)
         diag = np.ones((m, n))
+        if steps is not None:
+            steps["rho"], steps["ic"] = np.zeros((m, max(n - 1, 0)), dtype=ld), np.ones((m, max(n - 1, 0)), dtype=ld)
         for k in range(n):
             Lkk = u[:, k].astype(float)
             diag[:, k] = Lkk
@@ -128,12 +133,16 @@ def _cpu_gram(t, Z, n_sets):
                 u[new] = 1
                 v[new] = 0
             ic = 1 / np.sqrt((1 - rho) * (1 + rho))
+            if steps is not None:
+                steps["rho"][:, k], steps["ic"][:, k] = rho, ic
             us = u[:, k:n - 1]                                         # u shifted down by one
             vv = v[:, k + 1:]
             un = (us - rho[:, None] * vv) * ic[:, None]
             v[:, k + 1:] = (vv - rho[:, None] * us) * ic[:, None]
             u[:, k + 1:] = un
         good = info == 0
+        if steps is not None:
+            steps["last"] = u[:, n - 1].copy()
         sld = np.where(good, np.sum(np.log(np.where(good[:, None], diag, 1.0)), axis=1), np.nan)
         # the device's order (k_gram): 64 partial sums over the rows l, l + 64, ..., then a binary tree over them
         Yp = np.zeros((m, -(-n // 64) * 64, n_sets, cols))
@@ -180,3 +189,218 @@ def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None):
     if single:
         return G[0], float(sld[0]), int(info[0])
     return G, sld, info
+
+
+# ---- the gradient pieces ---------------------------------------------------------------------------------------
+
+def _cpu_inverse_column(steps, info):
+    """x = T^-1 e_0 (m, n) in long double from the recursion's reflection coefficients: Levinson's recursion in its normalised form.
+    A and B start as e_0 / sqrt(t_0) -- here e_0, the factor is taken off with the last pivot -- and a step rotates (A, shift(B)) as
+    the generator was rotated; A ends as the last row of L^-1 reversed, times sqrt(t_0)."""
+    ld = np.longdouble
+    rho, ic, last = steps["rho"], steps["ic"], steps["last"]
+    m, n = rho.shape[0], rho.shape[1] + 1
+    A = np.zeros((m, n), dtype=ld)
+    A[:, 0] = 1
+    B = A.copy()
+    for k in range(1, n):
+        r, c = rho[:, k - 1, None], ic[:, k - 1, None]
+        Bs = np.concatenate([np.zeros((m, 1), dtype=ld), B[:, :k]], axis=1)
+        Ak = A[:, :k + 1]
+        A[:, :k + 1], B[:, :k + 1] = (Ak - r * Bs) * c, (Bs - r * Ak) * c
+    x = A / (last * steps["root"])[:, None]
+    x[info != 0] = np.nan
+    return x
+
+
+def _lower_times(a, w):
+    """L(a) w, L(a) the lower-triangular Toeplitz matrix of the first column a."""
+    return np.convolve(a, w)[:len(a)]
+
+
+def _lower_t_times(a, z):
+    """L(a)^T z."""
+    return np.convolve(a, z[::-1])[:len(a)][::-1]
+
+
+def _cpu_solve_columns(x, Z):
+    """alpha = T^-1 Z (n, c) in long double by the Gohberg-Semencul formula, x = T^-1 e_0."""
+    ld = np.longdouble
+    n = len(x)
+    xt = np.concatenate([[ld(0)], x[:0:-1]])
+    out = np.empty((n, Z.shape[1]), dtype=ld)
+    for c in range(Z.shape[1]):
+        z = Z[:, c].astype(ld)
+        out[:, c] = (_lower_times(x, _lower_t_times(x, z)) - _lower_times(xt, _lower_t_times(xt, z))) / x[0]
+    return out
+
+
+def _cpu_diagonal_sums(x):
+    """s_d = sum of the d-th diagonal of T^-1 = (1 / x_0) sum_m (n - d - 2 m) x_m x_{m+d} (long double)."""
+    ld = np.longdouble
+    n = len(x)
+    m = np.arange(n, dtype=ld)
+    return np.array([np.sum((n - d - 2 * m[:n - d]) * x[:n - d] * x[d:]) for d in range(n)], dtype=ld) / x[0]
+
+
+_cpu_last = {}                                                         # see _cpu_pieces
+
+
+def _cpu_pieces(t, dt, Z, n_sets, want):
+    """(G, sld, info, x, alpha, trace, H) of ``backend='cpu'``: ``want`` names what beyond the first three is computed (None otherwise).
+    Everything in ``numpy.longdouble``, rounded to fp64 at the end.  The recursion of the last first columns and alpha of the last
+    right-hand sides are kept, so that ``toeplitz_inverse_column``, ``toeplitz_solve`` and ``toeplitz_grad`` of one problem run them once."""
+    ld = np.longdouble
+    m, n = t.shape
+    key = (t.shape, t.tobytes())
+    memo = _cpu_last if _cpu_last.get("key") == key else None          # the last first columns' recursion: x, alpha per Z
+    G = sld = None
+    with np.errstate(all="ignore"):
+        if memo is None or "trace" in want:
+            steps = {}
+            G, sld, info = _cpu_gram(t, Z, n_sets, steps)
+        if memo is None:
+            steps["root"] = np.sqrt(np.where(info == 0, t[:, 0], 1.0).astype(ld))
+            x = _cpu_inverse_column(steps, info)
+            bad = (info == 0) & ~np.all(np.isfinite(x.astype(float)), axis=1)
+            info[bad] = n + 1
+            x[info != 0] = np.nan
+            _cpu_last.clear()
+            _cpu_last.update(key=key, x=x, info=info.copy(), alpha={})
+            memo = _cpu_last
+        x, info = memo["x"], memo["info"].copy()
+        good = info == 0
+        if G is not None:
+            G[~good], sld[~good] = np.nan, np.nan
+        alpha = trace = H = None
+        if "alpha" in want or "H" in want:
+            zkey = (Z.shape, Z.tobytes())
+            if zkey not in memo["alpha"]:
+                alpha = np.full((m, n, Z.shape[1]), np.nan, dtype=ld)
+                for i in np.flatnonzero(good):
+                    alpha[i] = _cpu_solve_columns(x[i], Z)
+                memo["alpha"].clear()
+                memo["alpha"][zkey] = alpha
+            alpha = memo["alpha"][zkey]
+        if "trace" in want:
+            P = dt.shape[1]
+            trace = np.full((m, P), np.nan)
+            for i in np.flatnonzero(good):
+                s = _cpu_diagonal_sums(x[i])
+                w = np.full(n, ld(2))
+                w[0] = 1
+                trace[i] = [float(np.sum(w * dt[i, p].astype(ld) * s)) for p in range(P)]
+        if "H" in want:
+            P, cols = dt.shape[1], Z.shape[1] // n_sets
+            H = np.full((m, n_sets, P, cols, cols), np.nan)
+            for i in np.flatnonzero(good):
+                for p in range(P):
+                    d = dt[i, p].astype(ld)
+                    Q = np.stack([_lower_times(d, alpha[i, :, c]) + _lower_t_times(d, alpha[i, :, c]) - d[0] * alpha[i, :, c]
+                                  for c in range(Z.shape[1])], axis=1)
+                    for s_ in range(n_sets):
+                        sl = slice(s_ * cols, (s_ + 1) * cols)
+                        Hs = alpha[i][:, sl].T @ Q[:, sl]
+                        H[i, s_, p] = np.triu(Hs) + np.triu(Hs, 1).T
+    return G, sld, info, x.astype(float), None if alpha is None else alpha.astype(float), trace, H
+
+
+def _first_columns(t):
+    t = np.asarray(t, dtype=float)
+    single = t.ndim == 1
+    t2 = np.ascontiguousarray(t[None] if single else t)
+    if t2.ndim != 2 or t2.shape[0] < 1 or t2.shape[1] < 1:
+        raise ValueError(f"t must have shape (n,) or (m, n), got {t.shape}")
+    return t2, single
+
+
+def toeplitz_inverse_column(t, device=None, backend=None):
+    """``(x, info)``: the first column ``x = T^-1 e_0`` of the inverse of the symmetric Toeplitz matrices with the first columns t, (n,)
+    or (m, n), and ``info`` as ``toeplitz_gram`` gives it, or n + 1 where the recursion went through but x is not finite.  x is NaN where
+    info is not 0.  By Gohberg and Semencul x fixes the whole inverse."""
+    t2, single = _first_columns(t)
+    if resolve_backend(backend) == "cpu":
+        _, _, info, x, _, _, _ = _cpu_pieces(t2, None, np.zeros((t2.shape[1], 1)), 1, ())
+    else:
+        from . import _toep_lib
+        x, _, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, None, want_x=True)
+    return (x[0], int(info[0])) if single else (x, info)
+
+
+def toeplitz_solve(t, Z, device=None, backend=None):
+    """``(alpha, info)``: ``alpha = T^-1 Z`` for the first columns t, (n,) or (m, n), and the right-hand sides Z, (n,) or (n, c): alpha
+    is (n, c) or (m, n, c), NaN where info is not 0.  Four triangular Toeplitz products per column (Gohberg-Semencul), O(n^2 c)."""
+    t2, single = _first_columns(t)
+    Z = np.asarray(Z, dtype=float)
+    if Z.ndim == 1:
+        Z = Z[:, None]
+    n = t2.shape[1]
+    if Z.ndim != 2 or Z.shape[0] != n or Z.shape[1] < 1:
+        raise ValueError(f"Z must have shape ({n}, c), got {Z.shape}")
+    if resolve_backend(backend) == "cpu":
+        _, _, info, _, alpha, _, _ = _cpu_pieces(t2, None, Z, 1, ("alpha",))
+    else:
+        from . import _toep_lib
+        _, alpha, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, Z, want_x=False)
+    return (alpha[0], int(info[0])) if single else (alpha, info)
+
+
+def toeplitz_grad(t, dt, Z, n_sets=1, device=None, backend=None):
+    """``(G, sum_log_diag, info, trace, H)``: ``toeplitz_gram``'s three and, for the derivative columns dt, (P, n) or (m, P, n) -- dT_p
+    is the symmetric Toeplitz matrix of ``dt[p]`` -- ``trace[p] = tr(T^-1 dT_p)`` and ``H[s, p] = alpha_s^T dT_p alpha_s`` with
+    ``alpha_s = T^-1 Z_s`` (exactly symmetric): what ``lml_grad_from_gram`` takes.  Shapes: t (n,) gives trace (P,) and H (n_sets, P, c,
+    c); t (m, n) gives (m, P) and (m, n_sets, P, c, c).  Where info is not 0 (n + 1: the inverse's first column is not finite) all
+    outputs are NaN.  G, sum_log_diag and info are bit for bit ``toeplitz_gram``'s."""
+    t2, single = _first_columns(t)
+    m, n = t2.shape
+    dt = np.asarray(dt, dtype=float)
+    dt3 = np.ascontiguousarray(dt[None] if (single and dt.ndim == 2) else dt)
+    if dt3.ndim != 3 or dt3.shape[0] != m or dt3.shape[2] != n:
+        raise ValueError(f"dt must have shape (P, {n}) for one first column or ({m}, P, {n}), got {dt.shape}")
+    if dt3.shape[1] < 1:
+        raise ValueError("dt must hold at least one derivative column (P >= 1)")
+    Z = np.asarray(Z, dtype=float)
+    if Z.ndim == 1:
+        Z = Z[:, None]
+    n_sets = int(n_sets)
+    if Z.ndim != 2 or Z.shape[0] != n or n_sets < 1 or Z.shape[1] < 1 or Z.shape[1] % n_sets:
+        raise ValueError(f"Z must have shape ({n}, n_sets * c) with n_sets = {n_sets}, got {Z.shape}")
+    cols = Z.shape[1] // n_sets
+    if cols > GSUM_MAX_RHS:
+        raise ValueError(f"a set takes at most {GSUM_MAX_RHS} columns, got {cols}")
+    if resolve_backend(backend) == "cpu":
+        G, sld, info, _, _, trace, H = _cpu_pieces(t2, dt3, Z, n_sets, ("trace", "H"))
+    else:
+        from . import _toep_lib
+        G, sld, info, trace, H = _toep_lib.default_handle(resolve_device(device)).grad(t2, dt3, Z, n_sets)
+    if single:
+        return G[0], float(sld[0]), int(info[0]), trace[0], H[0]
+    return G, sld, info, trace, H
+
+
+def toeplitz_gradient_columns(kernel, X, theta=None, block=256):
+    """``dt`` (P, n): column 0 of scikit-learn's ``kernel(X, eval_gradient=True)[1]`` in theta order, for a stationary scikit-learn
+    kernel on the points X, shape (n,) or (n, 1); ``theta`` (log-transformed, default the kernel's own) is set on a clone.  Evaluated on
+    the host in blocks of ``block`` points together with X_0, so nothing n x n is formed; the entries are entrywise functions of the
+    pair, so this is the dense column bit for bit.  ``dt[p, 0]`` is the diagonal's derivative: a free WhiteKernel contributes its noise
+    level, a nugget nothing.  Refuses what ``toeplitz_column`` refuses."""
+    from sklearn.base import clone
+    X = np.asarray(X, dtype=float)
+    if X.ndim == 1:
+        X = X[:, None]
+    if X.ndim != 2 or X.shape[1] != 1 or X.shape[0] < 1:
+        raise ValueError(f"the Toeplitz path takes one feature: X must have shape (n,) or (n, 1), got {X.shape}")
+    if not _is_stationary(describe_kernel(kernel, 1)):
+        raise NotImplementedError("the Toeplitz path needs a stationary kernel: this one has a DotProduct leaf")
+    if theta is not None:
+        kernel = clone(kernel)
+        kernel.theta = np.asarray(theta, dtype=float)
+    n, P = X.shape[0], kernel.n_dims
+    out = np.empty((P, n))
+    if P == 0:
+        return out
+    out[:, 0] = kernel(X[:1], eval_gradient=True)[1][0, 0, :]
+    for a in range(1, n, block):
+        b = min(n, a + block)
+        out[:, a:b] = kernel(np.vstack([X[:1], X[a:b]]), eval_gradient=True)[1][1:, 0, :].T
+    return out

@@ -110,13 +110,18 @@ class TruncationGP:
         return y_mean, np.sqrt(self._cov_diag(X, start=order + 1))
 
     # -- fit (models.py:1367-1387) -------------------------------------------------------------------
-    def fit(self, X, y, orders, dX=None, dy=None):
+    def fit(self, X, y, orders, dX=None, dy=None, structure=None):
+        """``structure="toeplitz"``: the calibration of the coefficients' process runs on the structured route
+        (``ConjugateGaussianProcess.fit``); everything after it stays dense."""
         for name, fn in (("ratio", lambda: self.ratio(X, **self.ratio_kws)), ("ref", lambda: self.ref(X))):
             if np.atleast_1d(fn()).ndim > 1:
                 raise ValueError(f'{name} must return a 1d array or a scalar')            # models.py:1379-1382
         self.X_train_, self.y_train_, self.orders_, self.dX_, self.dy_ = X, y, orders, dX, dy
         self.coeffs_, _ = self._coeffs_and_jacobian(X, y, orders, self.ratio_kws)
-        self.coeffs_process.fit(X=X, y=self.coeffs_)
+        if structure is None:
+            self.coeffs_process.fit(X=X, y=self.coeffs_)
+        else:
+            self.coeffs_process.fit(X=X, y=self.coeffs_, structure=structure)
         self._fit = True
         return self
 

@@ -32,6 +32,31 @@
  *
  * gsum_toep_times: ms[0..3] = device time in milliseconds (HIP events) the handle has spent so far in: 0 host-to-device copies,
  *   1 the recursion with its forward substitution, 2 the Gram matrices, 3 device-to-host copies.  reset != 0 zeroes them.
+ *   Calls of gsum_toep_gram alone are charged here.
+ *
+ * The gradient of a likelihood also needs tr(T^-1 dT_p) and alpha^T dT_p alpha, alpha = T^-1 Z, for the derivative dT_p of T by each
+ * hyperparameter p -- itself symmetric Toeplitz, with the first column dt_p.  Both follow from x = T^-1 e_0, the first column of the
+ * inverse (Gohberg-Semencul: T^-1 = (1 / x_0) [L(x) L(x)^T - L(xt) L(xt)^T], L(.) lower-triangular Toeplitz, xt = (0, x_{n-1}, ..,
+ * x_1)), which Levinson's recursion in its normalised form yields from the reflection coefficients the Schur recursion has formed
+ * already: a second pass of n barrier-separated steps per first column, in double-double, replaying the coefficients.  Then the sums
+ * s_d = (1 / x_0) sum_m (n - d - 2 m) x_m x_{m+d} of the diagonals of T^-1 give the traces, four triangular Toeplitz products per
+ * column give alpha, and a Toeplitz product and a dot product give each entry of H; every sum is accumulated in double-double in an
+ * order fixed by n alone (alpha itself is rounded to fp64), so the determinism stated above for G holds for every output here.
+ *
+ * gsum_toep_grad: t, Z, n_sets, cols, G_out, sld_out, info_out as gsum_toep_gram, and bit for bit its results.  dt is m x P x n
+ *   row-major, P >= 1 derivative columns per first column.  Per first column i:
+ *     trace_out[i, p] = tr(T_i^-1 dT_ip)                                   (m x P)
+ *     H_out[i, s, p]  = alpha_s^T dT_ip alpha_s,  alpha_s = T_i^-1 Z_s     (m x n_sets x P x cols x cols, exactly symmetric)
+ *   info_out[i] = n + 1: the recursion went through but x is not finite.  Where info_out[i] != 0 every output of i is NaN.
+ *   Refused: what gsum_toep_gram refuses, a null pointer, P < 1 or P > 65535.
+ *
+ * gsum_toep_solve: x_out[i] = T_i^-1 e_0 (m x n) and alpha_out[i] = T_i^-1 Z (m x n x ncols row-major; Z is n x ncols column-major,
+ *   ncols >= 1 with no limit but n * ncols < 2^31).  Either output may be NULL (then so may Z, with alpha_out), not both.  info_out
+ *   as above; NaN where it is not 0.  The column scaling of gsum_toep_gram applies to alpha: the scale of Z is free.
+ *
+ * gsum_toep_grad_times: ms[0..7] = device milliseconds spent by gsum_toep_grad and gsum_toep_solve in: 0 host-to-device copies, 1 the
+ *   Schur recursion, 2 the coefficients and Levinson's recursion, 3 the Gram matrices, 4 the diagonal sums and traces, 5 the
+ *   Gohberg-Semencul products (alpha), 6 the Toeplitz products and contractions of H, 7 device-to-host copies.
  */
 #ifndef GSUM_TOEP_H
 #define GSUM_TOEP_H
@@ -53,6 +78,11 @@ int64_t gsum_toep_max_n(const gsum_toep* h);
 int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
                    double* sld_out, int32_t* info_out);
 int gsum_toep_times(gsum_toep* h, double* ms, int32_t reset);
+int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z, int64_t n_sets,
+                   int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out);
+int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* x_out, double* alpha_out,
+                    int32_t* info_out);
+int gsum_toep_grad_times(gsum_toep* h, double* ms, int32_t reset);
 
 #ifdef __cplusplus
 }
