@@ -45,6 +45,7 @@ class DeviceLoo(DeviceHandle):
     operations of include/gsum_loo.h on it.  ValueError where L's diagonal is not finite and positive or the matrix does not fit."""
 
     _free = "gsum_loo_free"
+    _last_error = "gsum_loo_last_error"
 
     def __init__(self, device, L):
         self._lib = lib = load_library()
@@ -79,9 +80,7 @@ class DeviceLoo(DeviceHandle):
 
     def times(self, reset=False):
         """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
-        ms = np.zeros(len(PHASES))
-        _check(self._lib, self._lib.gsum_loo_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(PHASES, ms.tolist()))
+        return self._phase_times("gsum_loo_times", PHASES, reset)
 
     def precision_block(self, idx):
         """The rows and columns ``idx`` of (L L^T)^-1, shape (g, g), in the order of ``idx``."""
@@ -118,6 +117,4 @@ class DeviceLoo(DeviceHandle):
 
     def fold_times(self, reset=False):
         """Device milliseconds spent so far in ``folds`` and ``precision_block``, by phase (FOLD_PHASES)."""
-        ms = np.zeros(len(FOLD_PHASES))
-        _check(self._lib, self._lib.gsum_loo_fold_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(FOLD_PHASES, ms.tolist()))
+        return self._phase_times("gsum_loo_fold_times", FOLD_PHASES, reset)

@@ -46,6 +46,7 @@ class DevicePointwise(DeviceHandle):
     include/gsum_pointwise.h on them.  ``orders`` are integers, ``mask`` flags the orders that are kept."""
 
     _free = "gsum_pointwise_free"
+    _last_error = "gsum_pointwise_last_error"
 
     def __init__(self, device, y, orders, mask):
         self._lib = lib = load_library()
@@ -101,6 +102,4 @@ class DevicePointwise(DeviceHandle):
 
     def times(self, reset=False):
         """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
-        ms = np.zeros(len(PHASES))
-        _check(self._lib, self._lib.gsum_pointwise_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(PHASES, ms.tolist()))
+        return self._phase_times("gsum_pointwise_times", PHASES, reset)

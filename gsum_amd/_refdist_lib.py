@@ -47,6 +47,7 @@ class DeviceRefDist(DeviceHandle):
     """One n x m matrix resident on the device (uploaded once) and the operations of include/gsum_refdist.h on it."""
 
     _free = "gsum_refdist_free"
+    _last_error = "gsum_refdist_last_error"
 
     def __init__(self, device, A):
         self._lib = lib = load_library()
@@ -93,6 +94,4 @@ class DeviceRefDist(DeviceHandle):
 
     def times(self, reset=False):
         """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
-        ms = np.zeros(len(PHASES))
-        _check(self._lib, self._lib.gsum_refdist_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(PHASES, ms.tolist()))
+        return self._phase_times("gsum_refdist_times", PHASES, reset)

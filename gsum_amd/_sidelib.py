@@ -1,5 +1,6 @@
-"""What the ctypes bindings of the side libraries share (_vario_lib.py, _refdist_lib.py; the C++ side of it is
-csrc/host/sidelib.hip.h): the prototype-attaching loader, the pointer helpers, the return-code check and the owner of a device handle."""
+"""What the ctypes bindings of the side libraries share (_vario_lib.py, _refdist_lib.py, _pointwise_lib.py, _loo_lib.py, _toep_lib.py;
+the C++ side of it is csrc/host/sidelib.hip.h): the prototype-attaching loader, the pointer helpers, the return-code check and the
+owner of a device handle, with the read-out of its phase clock."""
 from __future__ import annotations
 
 import ctypes as C
@@ -53,10 +54,18 @@ def check(lib, rc, last_error):
 
 class DeviceHandle:
     """Owner of one device handle ``_h`` of the library ``_lib``, freed by ``_free`` (the name of <library>_free): ``free()`` is
-    idempotent, and the context manager and ``__del__`` call it."""
+    idempotent, and the context manager and ``__del__`` call it.  A library with a phase clock names its <library>_last_error in
+    ``_last_error``; its binding's ``_handle()`` returns the open handle."""
 
     _free = None
+    _last_error = None
     _h = None
+
+    def _phase_times(self, fn_name, phases, reset):
+        """{phase: device milliseconds so far} from the library's ``fn_name`` (a <library>_*_times), in the order of ``phases``."""
+        ms = (C.c_double * len(phases))()
+        check(self._lib, getattr(self._lib, fn_name)(self._handle(), ms, int(bool(reset))), self._last_error)
+        return dict(zip(phases, ms))
 
     def free(self):
         if self._h is not None:

@@ -50,6 +50,7 @@ class DeviceToeplitz(DeviceHandle):
     """A handle of libgsum_toep.so on one device: its stream and its buffers, which grow with the calls."""
 
     _free = "gsum_toep_close"
+    _last_error = "gsum_toep_last_error"
 
     def __init__(self, device):
         self._lib = lib = load_library()
@@ -116,15 +117,11 @@ class DeviceToeplitz(DeviceHandle):
 
     def grad_times(self, reset=False):
         """Device milliseconds spent so far by ``grad`` and ``solve``, by phase (GRAD_PHASES)."""
-        ms = np.zeros(len(GRAD_PHASES))
-        _check(self._lib, self._lib.gsum_toep_grad_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(GRAD_PHASES, ms.tolist()))
+        return self._phase_times("gsum_toep_grad_times", GRAD_PHASES, reset)
 
     def times(self, reset=False):
         """Device milliseconds (HIP events) spent so far, by phase (PHASES)."""
-        ms = np.zeros(len(PHASES))
-        _check(self._lib, self._lib.gsum_toep_times(self._handle(), _d(ms), int(bool(reset))))
-        return dict(zip(PHASES, ms.tolist()))
+        return self._phase_times("gsum_toep_times", PHASES, reset)
 
 
 _handles = {}

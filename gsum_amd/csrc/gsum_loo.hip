@@ -19,67 +19,16 @@ constexpr int64_t kMaxGroups = 32768;              // the groups of one chunk: t
 
 }  // namespace
 
-struct gsum_loo : Handle {
+struct gsum_loo : TimedHandle<kAllPhases> {
     int64_t n = 0, N = 0;                          // the order of L, and n rounded up to loo::kBlock
     DevBuf<double> W;                              // N x N: the inverse of the padded factor
     DevBuf<double, true> R, Y;                     // N x ldr each: a chunk of right-hand sides and its forward product
     std::vector<double> p;                         // n
     double sum_log_diag = 0;
-    double ms[kAllPhases] = {};
     int64_t fold_budget = 0;                       // bytes one chunk of groups may take; 0: what hipMemGetInfo leaves
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
-    ~gsum_loo() {
-        for (auto& e : pending) {
-            (void)hipEventDestroy(e.second.first);
-            (void)hipEventDestroy(e.second.second);
-        }
-    }
 };
 
 namespace {
-
-// Run f (enqueues on h->stream) between two events charged to a phase; settle() turns them into milliseconds after the sync.
-template <class F>
-void timed(gsum_loo* h, Phase ph, F&& f) {
-    hipEvent_t a = nullptr, b = nullptr;
-    SL_CHECK(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        throw Error("hipEventCreate failed");
-    }
-    h->pending.push_back({(int)ph, {a, b}});
-    SL_CHECK(hipEventRecord(a, h->stream));
-    f();
-    SL_CHECK(hipEventRecord(b, h->stream));
-}
-
-void settle(gsum_loo* h) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    for (auto& p : h->pending) {
-        float t = 0.f;
-        if (e == hipSuccess && hipEventElapsedTime(&t, p.second.first, p.second.second) == hipSuccess) h->ms[p.first] += t;
-        (void)hipEventDestroy(p.second.first);
-        (void)hipEventDestroy(p.second.second);
-    }
-    h->pending.clear();
-    check(e, "hipStreamSynchronize");
-}
-
-// A call that throws between timed() and settle() must still drain the stream before its buffers can be touched again.
-template <class F>
-void run(gsum_loo* h, F&& f) {
-    SL_CHECK(hipSetDevice(h->device));
-    try {
-        f();
-        settle(h);
-    } catch (...) {
-        try {
-            settle(h);
-        } catch (...) {
-        }
-        throw;
-    }
-}
 
 // The levels of the recursive doubling above the diagonal blocks, for `count` matrices of leading dimension N, N * N elements apart
 // (sizes: their orders on the device, or nullptr for one matrix of order N).
@@ -559,20 +508,14 @@ GL_API int gsum_loo_folds(gsum_loo* h, const int64_t* fold_ptr, const int64_t* f
 GL_API int gsum_loo_fold_times(gsum_loo* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_loo_fold_times: null pointer argument");
-        for (int k = 0; k < kFoldPhases; ++k) {
-            ms[k] = h->ms[kPhases + k];
-            if (reset) h->ms[kPhases + k] = 0;
-        }
+        read_times(h, kPhases, kFoldPhases, ms, reset);
     });
 }
 
 GL_API int gsum_loo_times(gsum_loo* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_loo_times: null pointer argument");
-        for (int k = 0; k < kPhases; ++k) {
-            ms[k] = h->ms[k];
-            if (reset) h->ms[k] = 0;
-        }
+        read_times(h, 0, kPhases, ms, reset);
     });
 }
 

@@ -19,7 +19,7 @@ enum Phase { kH2D = 0, kDiff, kLogLike, kCoverage, kD2H, kPhases };
 
 }  // namespace
 
-struct gsum_pointwise : Handle {
+struct gsum_pointwise : TimedHandle<kPhases> {
     int64_t n = 0;
     int k = 0, kp = 0;
     double order_sum = 0;                          // the sum of the kept orders
@@ -27,60 +27,9 @@ struct gsum_pointwise : Handle {
     DevBuf<int> orders;                            // kp: the kept orders
     DevBuf<double, true> ratios, refs, partial, out, loc, scale, data, t;
     DevBuf<unsigned long long> counts;
-    double ms[kPhases] = {0, 0, 0, 0, 0};
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
-    ~gsum_pointwise() {
-        for (auto& e : pending) {
-            (void)hipEventDestroy(e.second.first);
-            (void)hipEventDestroy(e.second.second);
-        }
-    }
 };
 
 namespace {
-
-// Run f (enqueues on h->stream) between two events charged to a phase; settle() turns them into milliseconds after the sync.
-template <class F>
-void timed(gsum_pointwise* h, Phase ph, F&& f) {
-    hipEvent_t a = nullptr, b = nullptr;
-    SL_CHECK(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        throw Error("hipEventCreate failed");
-    }
-    h->pending.push_back({(int)ph, {a, b}});
-    SL_CHECK(hipEventRecord(a, h->stream));
-    f();
-    SL_CHECK(hipEventRecord(b, h->stream));
-}
-
-void settle(gsum_pointwise* h) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    for (auto& p : h->pending) {
-        float t = 0.f;
-        if (e == hipSuccess && hipEventElapsedTime(&t, p.second.first, p.second.second) == hipSuccess) h->ms[p.first] += t;
-        (void)hipEventDestroy(p.second.first);
-        (void)hipEventDestroy(p.second.second);
-    }
-    h->pending.clear();
-    check(e, "hipStreamSynchronize");
-}
-
-// A call that throws between timed() and settle() must still drain the stream before its buffers can be touched again.
-template <class F>
-void run(gsum_pointwise* h, F&& f) {
-    SL_CHECK(hipSetDevice(h->device));
-    try {
-        f();
-        settle(h);
-    } catch (...) {
-        try {
-            settle(h);
-        } catch (...) {
-        }
-        throw;
-    }
-}
 
 void upload(gsum_pointwise* h, double* dst, const double* src, size_t count) {
     SL_CHECK(hipMemcpyAsync(dst, src, sizeof(double) * count, hipMemcpyHostToDevice, h->stream));
@@ -218,10 +167,7 @@ GP_API int gsum_pointwise_coverage(gsum_pointwise* h, const double* loc, const d
 GP_API int gsum_pointwise_times(gsum_pointwise* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_pointwise_times: null pointer argument");
-        for (int k = 0; k < kPhases; ++k) {
-            ms[k] = h->ms[k];
-            if (reset) h->ms[k] = 0;
-        }
+        read_times(h, 0, kPhases, ms, reset);
     });
 }
 

@@ -17,68 +17,17 @@ enum Phase { kH2D = 0, kTranspose, kColSort, kPercentiles, kCoverage, kD2H, kPha
 
 }  // namespace
 
-struct gsum_refdist : Handle {
+struct gsum_refdist : TimedHandle<kPhases> {
     int64_t n = 0, m = 0;
     DevBuf<double> D, T;                           // the matrix (n x m) and the scratch matrix of the same size
     DevBuf<uint64_t> k0, k1;                       // long segments: the keys of every padded segment, ping and pong
     DevBuf<double> lower, upper, gamma, out;
     DevBuf<int64_t> idx;
     DevBuf<unsigned long long> counts;
-    double ms[kPhases] = {0, 0, 0, 0, 0, 0};
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
     bool lds_attr = false;
-    ~gsum_refdist() {
-        for (auto& e : pending) {
-            (void)hipEventDestroy(e.second.first);
-            (void)hipEventDestroy(e.second.second);
-        }
-    }
 };
 
 namespace {
-
-// Run f (enqueues on h->stream) between two events charged to a phase; settle() turns them into milliseconds after the sync.
-template <class F>
-void timed(gsum_refdist* h, Phase ph, F&& f) {
-    hipEvent_t a = nullptr, b = nullptr;
-    SL_CHECK(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        throw Error("hipEventCreate failed");
-    }
-    h->pending.push_back({(int)ph, {a, b}});
-    SL_CHECK(hipEventRecord(a, h->stream));
-    f();
-    SL_CHECK(hipEventRecord(b, h->stream));
-}
-
-void settle(gsum_refdist* h) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    for (auto& p : h->pending) {
-        float t = 0.f;
-        if (e == hipSuccess && hipEventElapsedTime(&t, p.second.first, p.second.second) == hipSuccess) h->ms[p.first] += t;
-        (void)hipEventDestroy(p.second.first);
-        (void)hipEventDestroy(p.second.second);
-    }
-    h->pending.clear();
-    check(e, "hipStreamSynchronize");
-}
-
-// A call that throws between timed() and settle() must still drain the stream before its buffers can be touched again.
-template <class F>
-void run(gsum_refdist* h, F&& f) {
-    SL_CHECK(hipSetDevice(h->device));
-    try {
-        f();
-        settle(h);
-    } catch (...) {
-        try {
-            settle(h);
-        } catch (...) {
-        }
-        throw;
-    }
-}
 
 void transpose(gsum_refdist* h, const double* in, int64_t rows, int64_t cols, double* out) {
     const int64_t tiles = ((rows + gr::kTile - 1) / gr::kTile) * ((cols + gr::kTile - 1) / gr::kTile);
@@ -274,10 +223,7 @@ GR_API int gsum_refdist_coverage(gsum_refdist* h, const double* lower, const dou
 GR_API int gsum_refdist_times(gsum_refdist* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_refdist_times: null pointer argument");
-        for (int k = 0; k < kPhases; ++k) {
-            ms[k] = h->ms[k];
-            if (reset) h->ms[k] = 0;
-        }
+        read_times(h, 0, kPhases, ms, reset);
     });
 }
 

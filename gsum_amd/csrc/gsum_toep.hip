@@ -22,133 +22,120 @@ constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y
 
 }  // namespace
 
-struct gsum_toep : Handle {
+struct gsum_toep : TimedHandle<kAllPhases> {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
     DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
-    double ms[kAllPhases] = {};
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;    // (phase, start, stop) of the call in flight
-    ~gsum_toep() {
-        for (auto& e : pending) {
-            (void)hipEventDestroy(e.second.first);
-            (void)hipEventDestroy(e.second.second);
-        }
-    }
 };
 
 namespace {
 
-// Run f (enqueues on h->stream) between two events charged to a phase; settle() turns them into milliseconds after the sync.
+// THE size classes, written here and nowhere else.  The generator elements per thread (E) and the columns of a chunk (C) follow from
+// n alone: registers hold E * (4 + 1.5 C) doubles (a residual and its fp32 correction word per column), or E * (2 + 1.5 C) in the
+// largest class, whose v lives in LDS (VL).
+template <int E_, int C_, bool VL_>
+struct SizeClass {
+    static constexpr int E = E_, C = C_;
+    static constexpr bool VL = VL_;
+};
+
+// f(SizeClass of n): what a launch instantiates its kernel from.
 template <class F>
-void timed(gsum_toep* h, int ph, F&& f) {
-    hipEvent_t a = nullptr, b = nullptr;
-    SL_CHECK(hipEventCreate(&a));
-    if (hipEventCreate(&b) != hipSuccess) {
-        (void)hipEventDestroy(a);
-        throw Error("hipEventCreate failed");
-    }
-    h->pending.push_back({(int)ph, {a, b}});
-    SL_CHECK(hipEventRecord(a, h->stream));
-    f();
-    SL_CHECK(hipEventRecord(b, h->stream));
-}
-
-void settle(gsum_toep* h) {
-    const hipError_t e = hipStreamSynchronize(h->stream);
-    for (auto& p : h->pending) {
-        float t = 0.f;
-        if (e == hipSuccess && hipEventElapsedTime(&t, p.second.first, p.second.second) == hipSuccess) h->ms[p.first] += t;
-        (void)hipEventDestroy(p.second.first);
-        (void)hipEventDestroy(p.second.second);
-    }
-    h->pending.clear();
-    check(e, "hipStreamSynchronize");
-}
-
-// A call that throws between timed() and settle() must still drain the stream before its buffers can be touched again.
-template <class F>
-void run(gsum_toep* h, F&& f) {
-    SL_CHECK(hipSetDevice(h->device));
-    try {
-        f();
-        settle(h);
-    } catch (...) {
-        try {
-            settle(h);
-        } catch (...) {
-        }
-        throw;
-    }
-}
-
-// The generator elements per thread (E) and the columns of a chunk (C) follow from n alone: registers hold E * (4 + 1.5 C) doubles
-// (a residual and its fp32 correction word per column), or E * (2 + 1.5 C) in the largest class, whose v lives in LDS.
-int chunk_cols(int64_t n) { return n <= 512 ? 16 : n <= 2048 ? 12 : n <= 4096 ? 5 : 3; }
-
-void launch_schur(gsum_toep* h, const double* t, int n, int ncols, int64_t m, double* Y, double* sld, int32_t* info) {
-    const int C = chunk_cols(n);
-    const dim3 grid((unsigned)((ncols + C - 1) / C), (unsigned)m);
-    hipStream_t st = h->stream;
+void with_size_class(int n, F&& f) {
     if (n <= gt::kThreads)
-        gt::k_schur<1, 16, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
+        f(SizeClass<1, 16, false>{});
     else if (n <= 4 * gt::kThreads)
-        gt::k_schur<4, 12, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
+        f(SizeClass<4, 12, false>{});
     else if (n <= 8 * gt::kThreads)
-        gt::k_schur<8, 5, false, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
+        f(SizeClass<8, 5, false>{});
     else
-        gt::k_schur<16, 3, true, false><<<grid, gt::kThreads, 0, st>>>(t, n, h->Z.p, h->ze.p, ncols, Y, sld, info, nullptr);
+        f(SizeClass<16, 3, true>{});
+}
+
+// The Schur recursion of m first columns with the forward substitution of the ncols columns Z / ze beside it.  R: it also hands out
+// its reflection coefficients and rotations (steps, (m, n, 4)), which launch_levinson replays.
+template <bool R>
+void launch_schur(gsum_toep* h, const double* t, int n, const double* Z, const int32_t* ze, int ncols, int64_t m, double* Y, double* sld,
+                  int32_t* info, double* steps) {
+    with_size_class(n, [&](auto k) {
+        using K = decltype(k);
+        const dim3 grid((unsigned)((ncols + K::C - 1) / K::C), (unsigned)m);       // the chunks of the C the kernel is made for
+        gt::k_schur<K::E, K::C, K::VL, R><<<grid, gt::kThreads, 0, h->stream>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
+    });
     SL_LAUNCHED("k_schur");
 }
 
-// The same recursion handing out its reflection coefficients and rotations (steps, (m, n, 4)), then the one that replays them into
-// x = T^-1 e_0 (xd both words, xf rounded).  Z / ze are the columns the forward substitution runs on.
-void launch_schur_steps(gsum_toep* h, const double* t, int n, const double* Z, const int32_t* ze, int ncols, int64_t m, double* Y,
-                        double* sld, int32_t* info, double* steps) {
-    // handing out the coefficients costs a few registers, which the value path's classes do not have to spare: fewer columns per
-    // chunk here (a column's solved values do not depend on its chunk)
-    const int C = chunk_cols(n);
-    const dim3 grid((unsigned)((ncols + C - 1) / C), (unsigned)m);
-    hipStream_t st = h->stream;
-    if (n <= gt::kThreads)
-        gt::k_schur<1, 16, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
-    else if (n <= 4 * gt::kThreads)
-        gt::k_schur<4, 12, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
-    else if (n <= 8 * gt::kThreads)
-        gt::k_schur<8, 5, false, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
-    else
-        gt::k_schur<16, 3, true, true><<<grid, gt::kThreads, 0, st>>>(t, n, Z, ze, ncols, Y, sld, info, steps);
-    SL_LAUNCHED("k_schur");
-}
-
+// The recursion that replays the steps into x = T^-1 e_0 (xd both words, xf rounded).
 void launch_levinson(gsum_toep* h, const double* t, int n, int64_t m, double* steps, double* xd, double* xf, double* sld, int32_t* info) {
     hipStream_t st = h->stream;
     gt::k_coeffs<<<dim3((unsigned)((n + 255) / 256), (unsigned)m), 256, 0, st>>>(steps, n, info);
     SL_LAUNCHED("k_coeffs");
-    if (n <= gt::kThreads)
-        gt::k_levinson<1><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
-    else if (n <= 4 * gt::kThreads)
-        gt::k_levinson<4><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
-    else if (n <= 8 * gt::kThreads)
-        gt::k_levinson<8><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
-    else
-        gt::k_levinson<16><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info);
+    with_size_class(n, [&](auto k) { gt::k_levinson<decltype(k)::E><<<(unsigned)m, gt::kThreads, 0, st>>>(t, n, steps, xd, xf, sld, info); });
     SL_LAUNCHED("k_levinson");
 }
 
-// What gsum_toep_gram refuses about the first columns, for the entry point `who`.
-void check_first_columns(const char* who, const double* t, int64_t m, int64_t n) {
-    if (m < 1 || n < 1) throw Error(std::string(who) + ": m and n must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n));
+// The exponents ze of the ncols columns of h->Z, which the kernels normalise by.
+void launch_colexp(gsum_toep* h, int n, int ncols) {
+    gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, h->stream>>>(h->Z.p, n, h->ze.p);
+    SL_LAUNCHED("k_colexp");
+}
+
+// G of cnt first columns from their solved columns h->Y.
+void launch_gram(gsum_toep* h, int n, int cols, int n_sets, int64_t cnt, const int32_t* info, double* G) {
+    gt::k_gram<<<dim3((unsigned)cols, (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, h->stream>>>(h->Y.p, n, cols, n_sets, h->ze.p, info, G);
+    SL_LAUNCHED("k_gram");
+}
+
+// G (gsz doubles per first column), sum_log_diag and info of m first columns to the host.
+void read_back(gsum_toep* h, int64_t m, size_t gsz, double* G_out, double* sld_out, int32_t* info_out) {
+    SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * gsz * m, hipMemcpyDeviceToHost, h->stream));
+    SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double) * m, hipMemcpyDeviceToHost, h->stream));
+    SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, h->stream));
+}
+
+// The first columns of one launch: as many as keep `bytes` each within kYBudget, a grid dimension's 65535 at most, one at least.
+int64_t columns_per_launch(int64_t m, size_t bytes) {
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / bytes)));
+}
+
+// What the entry point `who` refuses about the first columns: their order n ...
+void check_order(const char* who, int64_t n) {
     if (n > gt::kMaxN)
         throw Error(std::string(who) + ": n must be <= " + std::to_string(gt::kMaxN) + " (one workgroup holds the generator), got " + std::to_string(n));
+}
+
+// ... and their scale (`with`: what else the hint says to scale).  The right-hand sides are normalised on the device (k_colexp); the
+// scale of T reaches the fp32 correction word through lo(L) ~ 2^-53 sqrt(t0) and y ~ 1 / sqrt(t0), which stay far inside fp32's
+// range for t0 within 2^-64 .. 2^64.
+void check_scale(const char* who, const double* t, int64_t m, int64_t n, const char* with = "") {
     for (int64_t i = 0; i < m; ++i) {
         const double t0 = t[i * n];
         if (t0 > 0.0 && t0 < INFINITY && (t0 < 0x1p-64 || t0 > 0x1p64)) {
             char got[32];
             snprintf(got, sizeof got, "%g", t0);
-            throw Error(std::string(who) + ": t[0] must lie within 2^-64 .. 2^64 (scale t by a power of 4), got " + std::string(got) +
+            throw Error(std::string(who) + ": t[0] must lie within 2^-64 .. 2^64 (scale t by a power of 4" + with + "), got " + std::string(got) +
                         " in first column " + std::to_string(i));
         }
     }
+}
+
+// Both, after the counts, for grad and solve.  gram runs the two with its set checks between them, in the order it always refused in.
+void check_first_columns(const char* who, const double* t, int64_t m, int64_t n) {
+    if (m < 1 || n < 1) throw Error(std::string(who) + ": m and n must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n));
+    check_order(who, n);
+    check_scale(who, t, m, n);
+}
+
+void check_cols(const char* who, int32_t cols) {
+    if (cols < 1 || cols > gt::kMaxCols)
+        throw Error(std::string(who) + ": cols must be between 1 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(cols));
+}
+
+// What gram and grad refuse about the n_sets sets of cols columns (n >= 1): a grid dimension and the int indices of the kernels.
+void check_sets(const char* who, int64_t n, int64_t n_sets, int32_t cols) {
+    if (n_sets > 65535) throw Error(std::string(who) + ": n_sets must be <= 65535, got " + std::to_string(n_sets));
+    if (n_sets * cols > (((int64_t)1 << 31) - 1) / n)
+        throw Error(std::string(who) + ": n * n_sets * cols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(n_sets) + " x " + std::to_string(cols));
 }
 
 // alpha of cnt first columns from their xd: As (scaled columns) and, if not null, alpha_out (cnt, n, ncols).
@@ -181,27 +168,13 @@ GT_API int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, c
         if (!h || !t || !Z || !G_out || !sld_out || !info_out) throw Error("gsum_toep_gram: null pointer argument");
         if (m < 1 || n < 1 || n_sets < 1)
             throw Error("gsum_toep_gram: m, n and n_sets must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n) + ", " + std::to_string(n_sets));
-        if (cols < 1 || cols > gt::kMaxCols)
-            throw Error("gsum_toep_gram: cols must be between 1 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(cols));
-        if (n > gt::kMaxN)
-            throw Error("gsum_toep_gram: n must be <= " + std::to_string(gt::kMaxN) + " (one workgroup holds the generator), got " + std::to_string(n));
-        if (n_sets > 65535) throw Error("gsum_toep_gram: n_sets must be <= 65535, got " + std::to_string(n_sets));
-        if (n_sets * cols > (((int64_t)1 << 31) - 1) / n)
-            throw Error("gsum_toep_gram: n * n_sets * cols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(n_sets) + " x " + std::to_string(cols));
-        // The right-hand sides are normalised on the device (k_colexp); the scale of T reaches the fp32 correction word through
-        // lo(L) ~ 2^-53 sqrt(t0) and y ~ 1 / sqrt(t0), which stay far inside fp32's range for t0 within 2^-64 .. 2^64.
-        for (int64_t i = 0; i < m; ++i) {
-            const double t0 = t[i * n];
-            if (t0 > 0.0 && t0 < INFINITY && (t0 < 0x1p-64 || t0 > 0x1p64)) {
-                char got[32];
-                snprintf(got, sizeof got, "%g", t0);
-                throw Error("gsum_toep_gram: t[0] must lie within 2^-64 .. 2^64 (scale t by a power of 4 and G and sum_log_diag with it), got " +
-                            std::string(got) + " in first column " + std::to_string(i));
-            }
-        }
+        check_cols("gsum_toep_gram", cols);
+        check_order("gsum_toep_gram", n);
+        check_sets("gsum_toep_gram", n, n_sets, cols);
+        check_scale("gsum_toep_gram", t, m, n, " and G and sum_log_diag with it");
         const int ncols = (int)(n_sets * cols);
         const size_t per_theta = (size_t)n * ncols;                            // doubles of Y per first column
-        const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (per_theta * sizeof(double)))));
+        const int64_t step = columns_per_launch(m, per_theta * sizeof(double));
         const size_t gsz = (size_t)n_sets * cols * cols;
         run(h, [&] {
             h->t.reserve((size_t)m * n);
@@ -216,24 +189,16 @@ GT_API int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, c
                 SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
                 SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
             });
-            timed(h, kSchur, [&] {
-                gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
-                SL_LAUNCHED("k_colexp");
-            });
+            timed(h, kSchur, [&] { launch_colexp(h, (int)n, ncols); });
             for (int64_t lo = 0; lo < m; lo += step) {
                 const int64_t cnt = std::min(step, m - lo);
-                timed(h, kSchur, [&] { launch_schur(h, h->t.p + lo * n, (int)n, ncols, cnt, h->Y.p, h->sld.p + lo, h->info.p + lo); });
-                timed(h, kGram, [&] {
-                    gt::k_gram<<<dim3((unsigned)cols, (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(h->Y.p, (int)n, cols, (int)n_sets,
-                                                                                                         h->ze.p, h->info.p + lo, h->G.p + gsz * lo);
-                    SL_LAUNCHED("k_gram");
+                int32_t* il = h->info.p + lo;
+                timed(h, kSchur, [&] {
+                    launch_schur<false>(h, h->t.p + lo * n, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, nullptr);
                 });
+                timed(h, kGram, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
             }
-            timed(h, kD2H, [&] {
-                SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * gsz * m, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-            });
+            timed(h, kD2H, [&] { read_back(h, m, gsz, G_out, sld_out, info_out); });
         });
     });
 }
@@ -241,10 +206,7 @@ GT_API int gsum_toep_gram(gsum_toep* h, const double* t, int64_t m, int64_t n, c
 GT_API int gsum_toep_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_times: null pointer argument");
-        for (int k = 0; k < kPhases; ++k) {
-            ms[k] = h->ms[k];
-            if (reset) h->ms[k] = 0;
-        }
+        read_times(h, 0, kPhases, ms, reset);
     });
 }
 
@@ -254,16 +216,13 @@ GT_API int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, c
         if (!h || !t || !dt || !Z || !G_out || !sld_out || !info_out || !trace_out || !H_out) throw Error("gsum_toep_grad: null pointer argument");
         if (n_sets < 1) throw Error("gsum_toep_grad: n_sets must be >= 1, got " + std::to_string(n_sets));
         if (P < 1 || P > 65535) throw Error("gsum_toep_grad: P must be between 1 and 65535, got " + std::to_string(P));
-        if (cols < 1 || cols > gt::kMaxCols)
-            throw Error("gsum_toep_grad: cols must be between 1 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(cols));
+        check_cols("gsum_toep_grad", cols);
         check_first_columns("gsum_toep_grad", t, m, n);
-        if (n_sets > 65535) throw Error("gsum_toep_grad: n_sets must be <= 65535, got " + std::to_string(n_sets));
-        if (n_sets * cols > (((int64_t)1 << 31) - 1) / n)
-            throw Error("gsum_toep_grad: n * n_sets * cols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(n_sets) + " x " + std::to_string(cols));
+        check_sets("gsum_toep_grad", n, n_sets, cols);
         if ((int64_t)cols * cols * P > ((int64_t)1 << 31) - 1) throw Error("gsum_toep_grad: cols * cols * P must be < 2^31");
         const int ncols = (int)(n_sets * cols);
         const size_t per_theta = (size_t)n * ncols;                            // doubles of Y, and of alpha, per first column
-        const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (2 * per_theta * sizeof(double)))));
+        const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
         const size_t gsz = (size_t)n_sets * cols * cols, hsz = gsz * (size_t)P;
         run(h, [&] {
             h->t.reserve((size_t)m * n);
@@ -289,21 +248,14 @@ GT_API int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, c
                 SL_CHECK(hipMemcpyAsync(h->dt.p, dt, sizeof(double) * m * P * n, hipMemcpyHostToDevice, st));
                 SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
             });
-            timed(h, kGSchur, [&] {
-                gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
-                SL_LAUNCHED("k_colexp");
-            });
+            timed(h, kGSchur, [&] { launch_colexp(h, (int)n, ncols); });
             for (int64_t lo = 0; lo < m; lo += step) {
                 const int64_t cnt = std::min(step, m - lo);
                 const double* tl = h->t.p + lo * n;
                 int32_t* il = h->info.p + lo;
-                timed(h, kGSchur, [&] { launch_schur_steps(h, tl, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, kGSchur, [&] { launch_schur<true>(h, tl, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
                 timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p, h->sld.p + lo, il); });
-                timed(h, kGGram, [&] {
-                    gt::k_gram<<<dim3((unsigned)cols, (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(h->Y.p, (int)n, cols, (int)n_sets,
-                                                                                                         h->ze.p, il, h->G.p + gsz * lo);
-                    SL_LAUNCHED("k_gram");
-                });
+                timed(h, kGGram, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
                 timed(h, kGDiag, [&] {
                     gt::k_diagsums<<<dim3((unsigned)n, (unsigned)cnt), gt::kWave, 0, st>>>(h->xd.p, (int)n, il, h->sd.p);
                     SL_LAUNCHED("k_diagsums");
@@ -322,11 +274,9 @@ GT_API int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, c
                 });
             }
             timed(h, kGD2H, [&] {
-                SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * gsz * m, hipMemcpyDeviceToHost, st));
+                read_back(h, m, gsz, G_out, sld_out, info_out);
                 SL_CHECK(hipMemcpyAsync(H_out, h->H.p, sizeof(double) * hsz * m, hipMemcpyDeviceToHost, st));
                 SL_CHECK(hipMemcpyAsync(trace_out, h->trace.p, sizeof(double) * m * P, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
             });
         });
     });
@@ -343,7 +293,7 @@ GT_API int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, 
             throw Error("gsum_toep_solve: n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
         const int ncols = (int)nc;
         const size_t per_theta = (size_t)n * std::max(ncols, 1);
-        const int64_t step = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / (2 * per_theta * sizeof(double)))));
+        const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
         run(h, [&] {
             h->t.reserve((size_t)m * n);
             h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
@@ -369,16 +319,12 @@ GT_API int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, 
                 SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
                 SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
             });
-            if (ncols)
-                timed(h, kGSchur, [&] {
-                    gt::k_colexp<<<(unsigned)ncols, gt::kWave, 0, st>>>(h->Z.p, (int)n, h->ze.p);
-                    SL_LAUNCHED("k_colexp");
-                });
+            if (ncols) timed(h, kGSchur, [&] { launch_colexp(h, (int)n, ncols); });
             for (int64_t lo = 0; lo < m; lo += step) {
                 const int64_t cnt = std::min(step, m - lo);
                 const double* tl = h->t.p + lo * n;
                 int32_t* il = h->info.p + lo;
-                timed(h, kGSchur, [&] { launch_schur_steps(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, kGSchur, [&] { launch_schur<true>(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
                 timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
                 if (ncols) {
                     timed(h, kGSolve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
@@ -398,9 +344,6 @@ GT_API int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, 
 GT_API int gsum_toep_grad_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_grad_times: null pointer argument");
-        for (int k = kPhases; k < kAllPhases; ++k) {
-            ms[k - kPhases] = h->ms[k];
-            if (reset) h->ms[k] = 0;
-        }
+        read_times(h, kPhases, kAllPhases - kPhases, ms, reset);
     });
 }

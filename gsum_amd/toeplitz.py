@@ -62,6 +62,16 @@ def _context(device, backend):
     return default_context(resolve_device(device))
 
 
+def _one_feature(X):
+    """X as (n, 1), from (n,) or (n, 1)."""
+    X = np.asarray(X, dtype=float)
+    if X.ndim == 1:
+        X = X[:, None]
+    if X.ndim != 2 or X.shape[1] != 1 or X.shape[0] < 1:
+        raise ValueError(f"the Toeplitz path takes one feature: X must have shape (n,) or (n, 1), got {X.shape}")
+    return X
+
+
 def column_of_desc(ctx, desc, X, nugget=0.0):
     """``toeplitz_column`` for a descriptor on a context: column 0 of the two-argument build, the one-argument diagonal on top."""
     if not _is_stationary(desc):
@@ -77,11 +87,7 @@ def toeplitz_column(kernel, X, nugget=0.0, device=None, backend=None):
     (``kernel_matrix(desc, X, X[:1])``: bit for bit column 0 of the dense matrix), and ``t[0]`` is the one-argument diagonal, WhiteKernel
     noise included, plus ``nugget``.  X is not checked for uniformity here (``uniform_grid_step``).  NotImplementedError for a kernel
     with a non-stationary leaf (DotProduct), ValueError for more than one feature."""
-    X = np.asarray(X, dtype=float)
-    if X.ndim == 1:
-        X = X[:, None]
-    if X.ndim != 2 or X.shape[1] != 1 or X.shape[0] < 1:
-        raise ValueError(f"the Toeplitz path takes one feature: X must have shape (n,) or (n, 1), got {X.shape}")
+    X = _one_feature(X)
     desc = kernel if isinstance(kernel, KernelDesc) else describe_kernel(kernel, 1)
     return column_of_desc(_context(device, backend), desc, X, nugget)
 
@@ -158,6 +164,29 @@ def _cpu_gram(t, Z, n_sets, steps=None):
     return G, sld, info
 
 
+def _first_columns(t):
+    t = np.asarray(t, dtype=float)
+    single = t.ndim == 1
+    t2 = np.ascontiguousarray(t[None] if single else t)
+    if t2.ndim != 2 or t2.shape[0] < 1 or t2.shape[1] < 1:
+        raise ValueError(f"t must have shape (n,) or (m, n), got {t.shape}")
+    return t2, single
+
+
+def _rhs_sets(Z, n, n_sets):
+    """(Z (n, n_sets * c), n_sets, c) of the right-hand sides of ``toeplitz_gram`` and ``toeplitz_grad``; (n,) is one column."""
+    Z = np.asarray(Z, dtype=float)
+    if Z.ndim == 1:
+        Z = Z[:, None]
+    n_sets = int(n_sets)
+    if Z.ndim != 2 or Z.shape[0] != n or n_sets < 1 or Z.shape[1] < 1 or Z.shape[1] % n_sets:
+        raise ValueError(f"Z must have shape ({n}, n_sets * c) with n_sets = {n_sets}, got {Z.shape}")
+    cols = Z.shape[1] // n_sets
+    if cols > GSUM_MAX_RHS:
+        raise ValueError(f"a set takes at most {GSUM_MAX_RHS} columns, got {cols}")
+    return Z, n_sets, cols
+
+
 def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None):
     """``(G, sum_log_diag, info)`` of the symmetric Toeplitz matrices with the first columns t, (n,) or (m, n), and the right-hand sides
     Z, (n, n_sets * c) in ``n_sets`` sets of c <= 16 columns: ``G[s] = Z_s^T T^-1 Z_s`` (c x c), ``sum_log_diag = sum_j log L_jj`` of
@@ -166,21 +195,8 @@ def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None):
     ValueError beyond ``toeplitz_max_n()`` on the device: nothing falls back to a dense evaluation.  On the device the scale of Z is
     free (each column is normalised by a power of two and G scaled back, both exactly), while a positive finite ``t[0]`` outside
     2^-64 .. 2^64 is a ValueError: scale t by a power of 4 instead."""
-    t = np.asarray(t, dtype=float)
-    single = t.ndim == 1
-    t2 = np.ascontiguousarray(t[None] if single else t)
-    Z = np.asarray(Z, dtype=float)
-    if Z.ndim == 1:
-        Z = Z[:, None]
-    if t2.ndim != 2 or t2.shape[0] < 1 or t2.shape[1] < 1:
-        raise ValueError(f"t must have shape (n,) or (m, n), got {t.shape}")
-    n = t2.shape[1]
-    n_sets = int(n_sets)
-    if Z.ndim != 2 or Z.shape[0] != n or n_sets < 1 or Z.shape[1] < 1 or Z.shape[1] % n_sets:
-        raise ValueError(f"Z must have shape ({n}, n_sets * c) with n_sets = {n_sets}, got {Z.shape}")
-    cols = Z.shape[1] // n_sets
-    if cols > GSUM_MAX_RHS:
-        raise ValueError(f"a set takes at most {GSUM_MAX_RHS} columns, got {cols}")
+    t2, single = _first_columns(t)
+    Z, n_sets, cols = _rhs_sets(Z, t2.shape[1], n_sets)
     if resolve_backend(backend) == "cpu":
         G, sld, info = _cpu_gram(t2, Z, n_sets)
     else:
@@ -305,15 +321,6 @@ def _cpu_pieces(t, dt, Z, n_sets, want):
     return G, sld, info, x.astype(float), None if alpha is None else alpha.astype(float), trace, H
 
 
-def _first_columns(t):
-    t = np.asarray(t, dtype=float)
-    single = t.ndim == 1
-    t2 = np.ascontiguousarray(t[None] if single else t)
-    if t2.ndim != 2 or t2.shape[0] < 1 or t2.shape[1] < 1:
-        raise ValueError(f"t must have shape (n,) or (m, n), got {t.shape}")
-    return t2, single
-
-
 def toeplitz_inverse_column(t, device=None, backend=None):
     """``(x, info)``: the first column ``x = T^-1 e_0`` of the inverse of the symmetric Toeplitz matrices with the first columns t, (n,)
     or (m, n), and ``info`` as ``toeplitz_gram`` gives it, or n + 1 where the recursion went through but x is not finite.  x is NaN where
@@ -359,15 +366,7 @@ def toeplitz_grad(t, dt, Z, n_sets=1, device=None, backend=None):
         raise ValueError(f"dt must have shape (P, {n}) for one first column or ({m}, P, {n}), got {dt.shape}")
     if dt3.shape[1] < 1:
         raise ValueError("dt must hold at least one derivative column (P >= 1)")
-    Z = np.asarray(Z, dtype=float)
-    if Z.ndim == 1:
-        Z = Z[:, None]
-    n_sets = int(n_sets)
-    if Z.ndim != 2 or Z.shape[0] != n or n_sets < 1 or Z.shape[1] < 1 or Z.shape[1] % n_sets:
-        raise ValueError(f"Z must have shape ({n}, n_sets * c) with n_sets = {n_sets}, got {Z.shape}")
-    cols = Z.shape[1] // n_sets
-    if cols > GSUM_MAX_RHS:
-        raise ValueError(f"a set takes at most {GSUM_MAX_RHS} columns, got {cols}")
+    Z, n_sets, cols = _rhs_sets(Z, n, n_sets)
     if resolve_backend(backend) == "cpu":
         G, sld, info, _, _, trace, H = _cpu_pieces(t2, dt3, Z, n_sets, ("trace", "H"))
     else:
@@ -385,11 +384,7 @@ def toeplitz_gradient_columns(kernel, X, theta=None, block=256):
     pair, so this is the dense column bit for bit.  ``dt[p, 0]`` is the diagonal's derivative: a free WhiteKernel contributes its noise
     level, a nugget nothing.  Refuses what ``toeplitz_column`` refuses."""
     from sklearn.base import clone
-    X = np.asarray(X, dtype=float)
-    if X.ndim == 1:
-        X = X[:, None]
-    if X.ndim != 2 or X.shape[1] != 1 or X.shape[0] < 1:
-        raise ValueError(f"the Toeplitz path takes one feature: X must have shape (n,) or (n, 1), got {X.shape}")
+    X = _one_feature(X)
     if not _is_stationary(describe_kernel(kernel, 1)):
         raise NotImplementedError("the Toeplitz path needs a stationary kernel: this one has a DotProduct leaf")
     if theta is not None:

@@ -45,6 +45,10 @@ def test_a_failing_first_column_between_two_good_ones(n):
     record_parity(f"toeplitz_grad/failure_between_good/n{n}", info=gc.check_failure_between_good("hip", n))
 
 
+def test_first_columns_in_three_launches():
+    record_parity("toeplitz_grad/chunk_loop", info=gc.check_chunk_loop("hip"), **gc.CHUNKED)
+
+
 def test_refusals():
     gc.check_shape_refusals("hip")
     n = gm.toeplitz.toeplitz_max_n("hip") + 1

@@ -269,6 +269,46 @@ def check_failure_between_good(backend, n=513, d=0.25):
     return [int(v) for v in got[2]]
 
 
+CHUNKED = dict(n=513, c=16, n_sets=1023, m=3)
+
+
+def check_chunk_loop(backend):
+    """(4): toeplitz_cases.check_chunk_loop for ``toeplitz_grad`` and ``toeplitz_solve``, whose launches keep Y and alpha of a first
+    column in flight together: half the budget each.  n * ncols = 8 396 784 exceeds 2^28 / 32, so the three first columns go through one
+    per launch (offsets into t, dt, sum_log_diag, info, G, H, trace and alpha; the scratch reused), and one set fewer would take two:
+    the smallest such shape at c = 16 and an odd n above a class boundary.  P = 1.  The middle first column fails at step 3 and is NaN
+    throughout.  For each good one G, H and sum_log_diag of the first, middle and last set, and trace, are bitwise those of a call with
+    that column and those three sets alone, and alpha at their 48 columns bitwise that of such a call.  Device only (67 MB of Z, 200 MB
+    of alpha back): 0.4 s measured on an MI355X."""
+    n, c, n_sets, m = (CHUNKED[k] for k in ("n", "c", "n_sets", "m"))
+    half = tc.Y_BUDGET // 2
+    assert n * n_sets * c == 8396784 > 2 ** 28 // 32
+    assert tc.first_columns_per_launch(n, n_sets * c, m, half) == 1 and tc.first_columns_per_launch(n, (n_sets - 1) * c, m, half) == 2
+    goods = [tc.arfima_column(n, d) for d in tc.DS]
+    bad = goods[0].copy()
+    p = 2
+    bad[p] += 1.5 * float(tc.arfima_energies(n, tc.DS[0])[p - 1])
+    Z = np.asfortranarray(np.random.RandomState(11).standard_normal((n_sets * c, n)).T)
+    ts = np.stack([goods[0], bad, goods[1]])
+    dts = np.stack([np.cos(np.arange(n))[None]] * m)
+    got = gm.toeplitz_grad(ts, dts, Z, n_sets, backend=backend)
+    assert list(got[2]) == [0, p + 1, 0], got[2]
+    assert all(np.isnan(g[1]).all() for g in (got[0], got[1], got[3], got[4]))
+    al, ia = gm.toeplitz_solve(ts, Z, backend=backend)
+    assert list(ia) == [0, p + 1, 0] and np.isnan(al[1]).all()
+    pick = [0, n_sets // 2, n_sets - 1]
+    cols3 = np.concatenate([np.arange(s * c, (s + 1) * c) for s in pick])
+    Z3 = Z[:, cols3]
+    for i in (0, 2):
+        G1, s1, i1, tr1, H1 = gm.toeplitz_grad(ts[i], dts[i], Z3, 3, backend=backend)
+        assert i1 == 0 and np.array_equal(got[0][i][pick], G1) and np.array_equal(got[4][i][pick], H1), i
+        assert got[1][i] == s1 and np.array_equal(got[3][i], tr1), i
+        a1, j1 = gm.toeplitz_solve(ts[i], Z3, backend=backend)
+        assert j1 == 0 and np.array_equal(al[i][:, cols3], a1), i
+        assert np.isfinite(got[0][i]).all() and np.isfinite(got[4][i]).all() and np.isfinite(got[3][i]).all() and np.isfinite(a1).all()
+    return [int(v) for v in got[2]]
+
+
 def check_shape_refusals(backend):
     """(4): the shapes the Python layer refuses, on either backend."""
     import pytest
