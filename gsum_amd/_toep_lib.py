@@ -26,9 +26,13 @@ PROTOTYPES = {
                                  _dp]),
     "gsum_toep_solve": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_grad_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_toep_predict": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_loo": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_post_times": (C.c_int, [_p, _dp, C.c_int32]),
 }
 PHASES = ("h2d", "schur", "gram", "d2h")
 GRAD_PHASES = ("h2d", "schur", "levinson", "gram", "diagsums", "solve", "contract", "d2h")    # of grad and solve (gsum_toep_grad_times)
+POST_PHASES = ("h2d", "schur", "levinson", "sums", "cov", "solve", "d2h")                     # of predict and loo (gsum_toep_post_times)
 MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
 
 
@@ -114,6 +118,44 @@ class DeviceToeplitz(DeviceHandle):
             _check(self._lib, self._lib.gsum_toep_solve(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols,
                                                         None if x is None else _d(x), None if alpha is None else _d(alpha), _i32(info)))
         return x, alpha, info
+
+    def predict(self, t, K, Z, want_cov):
+        """(quad (q,), cross (q, c), cov (q, q) or None, G (c, c), sum_log_diag, info) of one first column t (n,), the cross-covariance
+        columns K (n, q) and the residual columns Z (n, c), c >= 0: gsum_toep_predict."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        Kf = np.asfortranarray(K, dtype=np.float64)
+        Zf = np.asfortranarray(Z, dtype=np.float64)
+        n, q, c = t.shape[0], Kf.shape[1], Zf.shape[1]
+        quad, cross, G = np.empty(q), np.empty((q, c)), np.empty((c, c))
+        cov = np.empty((q, q)) if want_cov else None
+        sld = np.empty(1)
+        info = np.empty(1, dtype=np.int32)
+        with self._lock:
+            _check(self._lib, self._lib.gsum_toep_predict(self._handle(), _d(t), n, _d(Kf), q, _d(Zf) if c else None, c, _d(quad),
+                                                          _d(cross) if c else None, None if cov is None else _d(cov), _d(G) if c else None,
+                                                          _d(sld), _i32(info)))
+        return quad, cross, cov, G, float(sld[0]), int(info[0])
+
+    def loo(self, t, Z):
+        """(p (m, n), alpha (m, n, c) or None, info): the diagonal of the inverse and T^-1 Z (Z None: p alone): gsum_toep_loo."""
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        m, n = t.shape
+        p = np.empty((m, n))
+        Zf = alpha = None
+        ncols = 0
+        if Z is not None:
+            Zf = np.asfortranarray(Z, dtype=np.float64)
+            ncols = Zf.shape[1]
+            alpha = np.empty((m, n, ncols))
+        info = np.empty(m, dtype=np.int32)
+        with self._lock:
+            _check(self._lib, self._lib.gsum_toep_loo(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, _d(p),
+                                                      None if alpha is None else _d(alpha), _i32(info)))
+        return p, alpha, info
+
+    def post_times(self, reset=False):
+        """Device milliseconds spent so far by ``predict`` and ``loo``, by phase (POST_PHASES)."""
+        return self._phase_times("gsum_toep_post_times", POST_PHASES, reset)
 
     def grad_times(self, reset=False):
         """Device milliseconds spent so far by ``grad`` and ``solve``, by phase (GRAD_PHASES)."""

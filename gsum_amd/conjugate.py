@@ -281,6 +281,7 @@ class ConjugateGaussianProcess:
         self.backend = resolve_backend(backend)
         self.batch_restarts = True   # multi-start fits advance in lock step, objective evaluations batched on the device
         self._fit_structure = None   # "toeplitz" while fit(structure="toeplitz") calibrates
+        self.structure_ = None       # "toeplitz" after fit(structure="toeplitz", dense_factor=False): no dense factor is held
         self._ctx = None
         self._L_dev = None          # device-resident Cholesky factor of kernel_(X_train_) + nugget
         self._replicas = {}         # ... and its copies on the other devices of predict(devices=...) (id(context) -> factor)
@@ -503,6 +504,8 @@ class ConjugateGaussianProcess:
         """(eig, Q) of corr_ + nugget I (models.py:714-715) -- an attribute of the 'eig' mode only, computed on the host when it is read."""
         if self.decomposition != 'eig' or not self._fit:
             return None
+        if self.structure_ is not None:
+            raise ValueError("the 'eig' attributes need the dense matrix: fit with dense_factor=True")
         if getattr(self, '_eigh_cache', None) is None:
             from scipy.linalg import eigh
             C = np.array(self.corr_, dtype=float)
@@ -818,12 +821,17 @@ class ConjugateGaussianProcess:
             return -float(values[best])
         return None
 
-    def fit(self, X, y, structure=None):
+    def fit(self, X, y, structure=None, dense_factor=True):
         """``structure="toeplitz"``: every objective evaluation of the calibration -- the single start's and the lock-step restarts' --
         runs on the structured route (``log_marginal_likelihood_batch(.., structure="toeplitz", eval_gradient=True)``); X must be a
         uniform one-dimensional grid and the kernel stationary, checked before the optimiser starts.  The final factorisation, the
-        posterior and ``predict`` stay dense."""
+        posterior and ``predict`` stay dense, unless ``dense_factor=False`` (with ``structure="toeplitz"`` alone): then the posterior
+        attributes come from ``toeplitz_gram`` of the fitted kernel's first column, no n x n matrix is built or factorised,
+        ``structure_`` is ``"toeplitz"`` and ``corr_L_`` None, and ``predict``, ``loo`` and ``sample_y`` follow the structured route
+        (DESIGN.md section 20).  ``kfold``, ``predict(devices=...)`` and the 'eig' attributes need the dense factor and say so."""
         self._check_decomposition()
+        if not dense_factor and structure != "toeplitz":
+            raise ValueError('dense_factor=False needs structure="toeplitz": there is no other route without the dense factor')
         if structure is not None:
             if structure != "toeplitz":
                 raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
@@ -838,11 +846,11 @@ class ConjugateGaussianProcess:
                 raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
         self._fit_structure = structure
         try:
-            return self._fit_dense_after_calibration(X, y)
+            return self._fit_dense_after_calibration(X, y, dense_factor)
         finally:
             self._fit_structure = None
 
-    def _fit_dense_after_calibration(self, X, y):
+    def _fit_dense_after_calibration(self, X, y, dense_factor=True):
         self.kernel_ = clone(self._default_kernel if self.kernel is None else self.kernel)   # models.py:685-688
         self._rng = check_random_state(self.random_state)
         if self.copy_X_train:
@@ -868,12 +876,22 @@ class ConjugateGaussianProcess:
         for rep in self._replicas.values():
             rep.free()
         self._replicas = {}
-        self._L_dev, info = ctx.factorize(desc, Xd, diag_add=self.nugget)
+        self._L_dev = None
+        self.structure_ = None
+        if dense_factor:
+            self._L_dev, info = ctx.factorize(desc, Xd, diag_add=self.nugget)
+        else:                                     # the structured route to the end: G and sum_log_diag of the fitted kernel's first column
+            from .toeplitz import column_of_desc, toeplitz_gram
+            G, sld, info = toeplitz_gram(column_of_desc(ctx, desc, Xd, self.nugget), Z, 1, device=self.device, backend=self.backend)
         if info != 0:
-            self._L_dev.free()
+            if self._L_dev is not None:
+                self._L_dev.free()
             self._L_dev = None
             raise np.linalg.LinAlgError("Matrix is not positive definite")    # numpy's message; models.py:711
-        if many:                                  # one forward solve per chunk of curves on the one factor (see _rhs_chunks)
+        if not dense_factor:
+            G = G[0]
+            self.structure_ = "toeplitz"
+        elif many:                                # one forward solve per chunk of curves on the one factor (see _rhs_chunks)
             y2 = np.asarray(self.y_train_, dtype=float)
             blocks, sld = [], None
             for idx, Zc in self._rhs_chunks(Xd, y2):
@@ -918,18 +936,47 @@ class ConjugateGaussianProcess:
         center = self.center_ if self._fit else self.center0
         return self.basis(X) @ center
 
-    def loo(self, y=None):
+    def loo(self, y=None, structure=None):
         """The plug-in leave-one-out predictions of the fitted process at its training points (``LooResult``; loo.py): mean =
         ``center_``, cov = ``cov_factor_`` (R + nugget I), whose factor is sqrt(``cov_factor_``) times the one ``fit`` holds.  ``y``,
-        (n,) or (n, n_curves), defaults to the training curves."""
+        (n,) or (n, n_curves), defaults to the training curves.  ``structure="toeplitz"`` (or ``structure_`` after
+        ``fit(dense_factor=False)``): ``toeplitz_loo`` of the first column ``cov_factor_ * t`` instead, without the factor."""
         if isinstance(self, ConjugateStudentProcess):
             raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out is not provided")
+        structure = self._structure_of(structure)
+        if structure is not None:
+            if not self._fit:
+                raise ValueError("loo needs a fitted process: call fit first")
+            from .toeplitz import toeplitz_loo
+            X = np.asarray(self.X_train_, dtype=float)
+            t = self._structured_column(self._context(), describe_kernel(self.kernel_, X.shape[1]), X)
+            return toeplitz_loo(float(np.squeeze(self.cov_factor_)) * t, self.y_train_ if y is None else y, self.mean(X),
+                                device=self.device, backend=self.backend)
         from .loo import loo_from_factor
         L, y, mean = self._plug_in(y, "loo")
         return loo_from_factor(L, y, mean=mean, device=self.device, backend=self.backend)
 
+    def _structure_of(self, structure):
+        """The route a call takes: its own ``structure=`` or, with None, the fit's ``structure_``."""
+        if structure is None:
+            return self.structure_ if self._fit else None
+        if structure != "toeplitz":
+            raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+        return structure
+
+    def _structured_column(self, ctx, desc, Xc):
+        """The first column of ``kernel_(Xc) + nugget I`` after the checks of the structured route: one feature, a uniform grid, a
+        stationary kernel."""
+        from .toeplitz import column_of_desc, uniform_grid_step
+        if Xc.ndim != 2 or Xc.shape[1] != 1:
+            raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: the conditioning points must have shape (n, 1), got {Xc.shape}')
+        uniform_grid_step(Xc)
+        return column_of_desc(ctx, desc, Xc, self.nugget)
+
     def _plug_in(self, y, who):
         """(factor, curves, mean) of the plug-in Gaussian at the training points."""
+        if self._fit and self._L_dev is None and self.structure_ is not None:
+            raise ValueError(f"{who} needs the dense factor: fit with dense_factor=True")
         if not self._fit or self._L_dev is None:
             raise ValueError(f"{who} needs a fitted process: call fit first")
         L = np.sqrt(float(np.squeeze(self.cov_factor_))) * self._L_dev.to_host()
@@ -971,13 +1018,19 @@ class ConjugateGaussianProcess:
         return y_mean
 
     # -- predict (models.py:753-845) ------------------------------------------------
-    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, devices=None):
+    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, devices=None, structure=None):
         """``devices`` (additive; ``"all"`` or a list of GPU indices): the new points are cut into one block per device
         (``gsum_shard_range``), every device factorises its own copy of the training matrix once (kept until the next ``fit``) and
         the blocks run side by side, one host thread per device -- columns of the predictive covariance are independent per new
         point (models.py:836), so mean and standard deviation equal the one-device call; ``return_cov`` needs all columns on one
-        device and is refused."""
-        return self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, False, devices=devices)[0]
+        device and is refused.
+
+        ``structure="toeplitz"`` (additive; with None the fit's ``structure_``): the three pieces the prediction is made of -- the
+        shifts, the column sums of squares and, with ``return_cov``, (L^-1 K)^T (L^-1 K) -- come from ``toeplitz_predict`` of the
+        first column of the conditioning matrix and the cross-covariance columns, which the main library builds; no n x n matrix is
+        built or factorised.  The conditioning points (``Xc``, or the training points) must be a uniform one-dimensional grid and
+        the kernel stationary; ``devices=`` is refused.  Everything after the three pieces is the dense route's host algebra."""
+        return self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, False, devices=devices, structure=structure)[0]
 
     def _group(self, devices):
         """The device group of ``devices=`` (process-wide, adopting the default contexts; ``backend='cpu'``: as many CPU contexts)."""
@@ -1001,9 +1054,9 @@ class ConjugateGaussianProcess:
             self._replicas[key] = L
         return L
 
-    def _predict_core(self, X, return_std, return_cov, Xc, y, pred_noise, want_basis, devices=None):
+    def _predict_core(self, X, return_std, return_cov, Xc, y, pred_noise, want_basis, devices=None, structure=None):
         """predict, plus (want_basis) the conditional basis 1 - R_no R^-1 1 of models.py:1168 from the same
-        triangular solve: one more right-hand-side column."""
+        triangular solve: one more right-hand-side column.  ``structure``: see ``predict``."""
         if return_std and return_cov:
             raise RuntimeError('Only one of return_std or return_cov may be True')
         if not self._fit:
@@ -1011,12 +1064,20 @@ class ConjugateGaussianProcess:
         self._check_decomposition()
         if devices is not None and return_cov:
             raise ValueError("return_cov needs every new point on one device: call predict without devices=")
+        structure = self._structure_of(structure)
+        if structure is not None and devices is not None:
+            raise ValueError('structure="toeplitz" runs on one device: devices= needs the dense route (a fit with dense_factor=True)')
         ctx = self._context()
         X = np.asarray(X, dtype=float)
         desc = describe_kernel(self.kernel_, X.shape[1])
         own = None
         fitted_inputs = Xc is None
-        if Xc is None:
+        t_col = None
+        if structure is not None:                                                 # no factor: the first column of the conditioning matrix
+            Xc = np.asarray(self.X_train_ if Xc is None else Xc, dtype=float)
+            t_col = self._structured_column(ctx, desc, Xc)
+            L = None
+        elif Xc is None:
             Xc = np.asarray(self.X_train_, dtype=float)
             L = self._L_dev
         elif devices is not None:
@@ -1050,7 +1111,15 @@ class ConjugateGaussianProcess:
                     cv_ = cv if wc else cv_
                 return np.concatenate(parts, axis=1), css, cv_
 
-            if devices is None:
+            if structure is not None:
+                from .toeplitz import toeplitz_predict
+                if resid.shape[1] > GSUM_MAX_RHS:
+                    raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS} residual columns, got {resid.shape[1]}')
+                got = toeplitz_predict(t_col, ctx.kernel_matrix(desc, Xc, X), resid, want_cov=return_cov, device=self.device, backend=self.backend)
+                if got.info != 0:
+                    raise np.linalg.LinAlgError("Matrix is not positive definite")
+                shifts, colsumsq, VtV = got.cross, got.quad, got.cov
+            elif devices is None:
                 shifts, colsumsq, VtV = terms(ctx, L, X, return_cov)
             else:
                 from .grid import shard_range
@@ -1172,8 +1241,8 @@ class ConjugateStudentProcess(ConjugateGaussianProcess):
         # corr + basis disp basis^T with the constant basis: an additive constant on top of the kernel
         return cov_factor(scale ** 2, df), describe_kernel(kernel, d).plus_constant(float(np.atleast_2d(disp)[0, 0]))
 
-    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False):   # models.py:1127-1184
-        pred, basis = self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, True)
+    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, structure=None):   # models.py:1127-1184
+        pred, basis = self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, True, structure=structure)
         if not self._fit:
             disp = self.disp0
             var = cov_factor(self.scale0 ** 2, self.df0)

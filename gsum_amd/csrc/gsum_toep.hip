@@ -17,15 +17,18 @@ namespace {
 enum Phase { kH2D = 0, kSchur, kGram, kD2H, kPhases };
 // the phases of gsum_toep_grad and gsum_toep_solve (gsum_toep_grad_times), after those of gsum_toep_gram in one array
 enum GradPhase { kGH2D = kPhases, kGSchur, kGLevinson, kGGram, kGDiag, kGSolve, kGContract, kGD2H, kAllPhases };
+// the phases of gsum_toep_predict and gsum_toep_loo (gsum_toep_post_times), after those
+enum PostPhase { kPH2D = kAllPhases, kPSchur, kPLevinson, kPSums, kPCov, kPSolve, kPD2H, kEveryPhase };
 
 constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y) in flight: the first columns go through in chunks
 
 }  // namespace
 
-struct gsum_toep : TimedHandle<kAllPhases> {
+struct gsum_toep : TimedHandle<kEveryPhase> {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
     DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
+    DevBuf<double, true> Yz, quad, cross, cov, pd;                             // the posterior's
 };
 
 namespace {
@@ -145,6 +148,78 @@ void launch_solve(gsum_toep* h, int n, int ncols, int64_t cnt, const double* xd,
     SL_LAUNCHED("k_gs_first");
     gt::k_gs_second<<<grid, gt::kWave, 0, h->stream>>>(xd, n, h->W.p, h->ze.p, ncols, info, h->As.p, alpha_out);
     SL_LAUNCHED("k_gs_second");
+}
+
+// The phases a call of solve_columns is charged to: gsum_toep_solve's are the gradient path's, gsum_toep_loo's the posterior's.
+struct SolvePhases {
+    int h2d, schur, levinson, solve, d2h;
+};
+
+// The body of gsum_toep_solve and gsum_toep_loo (`who`): x = T^-1 e_0 of m first columns by the recursion on one column of zeros and
+// Levinson's replay, then alpha = T^-1 Z (alpha_out not null) and p = diag(T^-1) (p_out not null) from it.
+void solve_columns(const char* who, const SolvePhases& ph, gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols64,
+                   double* x_out, double* alpha_out, double* p_out, int32_t* info_out) {
+    const std::string name(who);
+    if (alpha_out && ncols64 < 1) throw Error(name + ": ncols must be >= 1, got " + std::to_string(ncols64));
+    check_first_columns(who, t, m, n);
+    const int64_t nc = alpha_out ? ncols64 : 0;
+    if (nc > (((int64_t)1 << 31) - 1) / n) throw Error(name + ": n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
+    const int ncols = (int)nc;
+    const size_t per_theta = (size_t)n * std::max(ncols, 1);
+    const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
+    run(h, [&] {
+        h->t.reserve((size_t)m * n);
+        h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
+        h->ze.reserve((size_t)ncols + 1);
+        h->Y.reserve((size_t)n * step);
+        h->steps.reserve((size_t)4 * n * step);
+        h->xd.reserve((size_t)2 * n * step);
+        h->xf.reserve((size_t)n * m);
+        h->sld.reserve((size_t)m);
+        h->info.reserve((size_t)m);
+        if (p_out) h->pd.reserve((size_t)n * m);
+        if (ncols) {
+            h->As.reserve(per_theta * step);
+            h->Aout.reserve(per_theta * step);
+            h->W.reserve(4 * per_theta * step);
+        }
+        hipStream_t st = h->stream;
+        // the recursion needs no right-hand side here: it runs on one column of zeros, kept after the ncols of Z
+        double* zero = h->Z.p + (size_t)n * ncols;
+        int32_t* zero_e = h->ze.p + ncols;
+        timed(h, ph.h2d, [&] {
+            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+            if (ncols) SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * n * ncols, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
+            SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
+        });
+        if (ncols) timed(h, ph.schur, [&] { launch_colexp(h, (int)n, ncols); });
+        for (int64_t lo = 0; lo < m; lo += step) {
+            const int64_t cnt = std::min(step, m - lo);
+            const double* tl = h->t.p + lo * n;
+            int32_t* il = h->info.p + lo;
+            timed(h, ph.schur, [&] { launch_schur<true>(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+            timed(h, ph.levinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
+            if (p_out)
+                timed(h, ph.solve, [&] {
+                    with_size_class((int)n, [&](auto k) {
+                        gt::k_invdiag<decltype(k)::E><<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->xd.p, (int)n, il, h->pd.p + lo * n);
+                    });
+                    SL_LAUNCHED("k_invdiag");
+                });
+            if (ncols) {
+                timed(h, ph.solve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
+                timed(h, ph.d2h, [&] {
+                    SL_CHECK(hipMemcpyAsync(alpha_out + (size_t)lo * per_theta, h->Aout.p, sizeof(double) * per_theta * cnt, hipMemcpyDeviceToHost, st));
+                });
+            }
+        }
+        timed(h, ph.d2h, [&] {
+            if (x_out) SL_CHECK(hipMemcpyAsync(x_out, h->xf.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
+            if (p_out) SL_CHECK(hipMemcpyAsync(p_out, h->pd.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
+            SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+        });
+    });
 }
 
 }  // namespace
@@ -286,58 +361,7 @@ GT_API int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, 
                            double* alpha_out, int32_t* info_out) {
     return guarded([&] {
         if (!h || !t || !info_out || (!x_out && !alpha_out) || (alpha_out && !Z)) throw Error("gsum_toep_solve: null pointer argument");
-        if (alpha_out && ncols64 < 1) throw Error("gsum_toep_solve: ncols must be >= 1, got " + std::to_string(ncols64));
-        check_first_columns("gsum_toep_solve", t, m, n);
-        const int64_t nc = alpha_out ? ncols64 : 0;
-        if (nc > (((int64_t)1 << 31) - 1) / n)
-            throw Error("gsum_toep_solve: n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
-        const int ncols = (int)nc;
-        const size_t per_theta = (size_t)n * std::max(ncols, 1);
-        const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
-        run(h, [&] {
-            h->t.reserve((size_t)m * n);
-            h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
-            h->ze.reserve((size_t)ncols + 1);
-            h->Y.reserve((size_t)n * step);
-            h->steps.reserve((size_t)4 * n * step);
-            h->xd.reserve((size_t)2 * n * step);
-            h->xf.reserve((size_t)n * m);
-            h->sld.reserve((size_t)m);
-            h->info.reserve((size_t)m);
-            if (ncols) {
-                h->As.reserve(per_theta * step);
-                h->Aout.reserve(per_theta * step);
-                h->W.reserve(4 * per_theta * step);
-            }
-            hipStream_t st = h->stream;
-            // the recursion needs no right-hand side here: it runs on one column of zeros, kept after the ncols of Z
-            double* zero = h->Z.p + (size_t)n * ncols;
-            int32_t* zero_e = h->ze.p + ncols;
-            timed(h, kGH2D, [&] {
-                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
-                if (ncols) SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * n * ncols, hipMemcpyHostToDevice, st));
-                SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
-                SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
-            });
-            if (ncols) timed(h, kGSchur, [&] { launch_colexp(h, (int)n, ncols); });
-            for (int64_t lo = 0; lo < m; lo += step) {
-                const int64_t cnt = std::min(step, m - lo);
-                const double* tl = h->t.p + lo * n;
-                int32_t* il = h->info.p + lo;
-                timed(h, kGSchur, [&] { launch_schur<true>(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
-                timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
-                if (ncols) {
-                    timed(h, kGSolve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
-                    timed(h, kGD2H, [&] {
-                        SL_CHECK(hipMemcpyAsync(alpha_out + (size_t)lo * per_theta, h->Aout.p, sizeof(double) * per_theta * cnt, hipMemcpyDeviceToHost, st));
-                    });
-                }
-            }
-            timed(h, kGD2H, [&] {
-                if (x_out) SL_CHECK(hipMemcpyAsync(x_out, h->xf.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-            });
-        });
+        solve_columns("gsum_toep_solve", {kGH2D, kGSchur, kGLevinson, kGSolve, kGD2H}, h, t, m, n, Z, ncols64, x_out, alpha_out, nullptr, info_out);
     });
 }
 
@@ -345,5 +369,90 @@ GT_API int gsum_toep_grad_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_grad_times: null pointer argument");
         read_times(h, kPhases, kAllPhases - kPhases, ms, reset);
+    });
+}
+
+GT_API int gsum_toep_loo(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* p_out, double* alpha_out,
+                         int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !p_out || !info_out || (alpha_out && !Z)) throw Error("gsum_toep_loo: null pointer argument");
+        solve_columns("gsum_toep_loo", {kPH2D, kPSchur, kPLevinson, kPSolve, kPD2H}, h, t, m, n, Z, ncols, nullptr, alpha_out, p_out, info_out);
+    });
+}
+
+GT_API int gsum_toep_predict(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
+                             double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !K || !quad_out || !sld_out || !info_out) throw Error("gsum_toep_predict: null pointer argument");
+        if (q < 1 || n < 1) throw Error("gsum_toep_predict: n and q must be >= 1, got " + std::to_string(n) + ", " + std::to_string(q));
+        if (c < 0 || c > gt::kMaxCols)
+            throw Error("gsum_toep_predict: c must be between 0 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(c));
+        if (c > 0 && (!Z || !cross_out || !G_out)) throw Error("gsum_toep_predict: null pointer argument (Z, cross_out and G_out with c > 0)");
+        check_order("gsum_toep_predict", n);
+        if (q > (((int64_t)1 << 31) - 1) / n - c)
+            throw Error("gsum_toep_predict: n * (q + c) must be < 2^31, got " + std::to_string(n) + " x (" + std::to_string(q) + " + " + std::to_string(c) + ")");
+        if (cov_out && q > 16 * 65535) throw Error("gsum_toep_predict: cov_out takes q <= 1048560, got " + std::to_string(q));
+        check_scale("gsum_toep_predict", t, 1, n, " and the outputs with it");
+        const int ncols = (int)(q + c), qi = (int)q;
+        const size_t ny = (size_t)n * ncols;
+        run(h, [&] {
+            h->t.reserve((size_t)n);
+            h->Z.reserve(ny);
+            h->Y.reserve(ny);
+            h->ze.reserve((size_t)ncols);
+            h->sld.reserve(1);
+            h->info.reserve(1);
+            h->quad.reserve((size_t)q);
+            if (c) {
+                h->cross.reserve((size_t)q * c);
+                h->Yz.reserve((size_t)n * c);
+                h->G.reserve((size_t)c * c);
+            }
+            if (cov_out) h->cov.reserve((size_t)q * q);
+            hipStream_t st = h->stream;
+            timed(h, kPH2D, [&] {
+                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->Z.p, K, sizeof(double) * n * q, hipMemcpyHostToDevice, st));
+                if (c) SL_CHECK(hipMemcpyAsync(h->Z.p + (size_t)n * q, Z, sizeof(double) * n * c, hipMemcpyHostToDevice, st));
+            });
+            timed(h, kPSchur, [&] {
+                launch_colexp(h, (int)n, ncols);
+                launch_schur<false>(h, h->t.p, (int)n, h->Z.p, h->ze.p, ncols, 1, h->Y.p, h->sld.p, h->info.p, nullptr);
+            });
+            timed(h, kPSums, [&] {
+                gt::k_pred_sums<<<dim3((unsigned)q, (unsigned)(1 + c)), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->quad.p,
+                                                                                          h->cross.p);
+                SL_LAUNCHED("k_pred_sums");
+                if (c) {                                                       // the residual columns alone, as one set of k_gram's
+                    SL_CHECK(hipMemcpy2DAsync(h->Yz.p, sizeof(double) * c, h->Y.p + q, sizeof(double) * ncols, sizeof(double) * c, (size_t)n,
+                                              hipMemcpyDeviceToDevice, st));
+                    gt::k_gram<<<dim3((unsigned)c, 1, 1), gt::kWave, 0, st>>>(h->Yz.p, (int)n, c, 1, h->ze.p + q, h->info.p, h->G.p);
+                    SL_LAUNCHED("k_gram");
+                }
+            });
+            if (cov_out)
+                timed(h, kPCov, [&] {
+                    const unsigned tiles = (unsigned)((q + 15) / 16);
+                    gt::k_pred_cov<<<dim3(tiles, tiles), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->cov.p);
+                    SL_LAUNCHED("k_pred_cov");
+                });
+            timed(h, kPD2H, [&] {
+                SL_CHECK(hipMemcpyAsync(quad_out, h->quad.p, sizeof(double) * q, hipMemcpyDeviceToHost, st));
+                if (c) {
+                    SL_CHECK(hipMemcpyAsync(cross_out, h->cross.p, sizeof(double) * q * c, hipMemcpyDeviceToHost, st));
+                    SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * c * c, hipMemcpyDeviceToHost, st));
+                }
+                if (cov_out) SL_CHECK(hipMemcpyAsync(cov_out, h->cov.p, sizeof(double) * q * q, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double), hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            });
+        });
+    });
+}
+
+GT_API int gsum_toep_post_times(gsum_toep* h, double* ms, int32_t reset) {
+    return guarded([&] {
+        if (!h || !ms) throw Error("gsum_toep_post_times: null pointer argument");
+        read_times(h, kAllPhases, kEveryPhase - kAllPhases, ms, reset);
     });
 }

@@ -23,6 +23,8 @@
 // The gradient pieces (the comments stand at the kernels): k_schur<.., R = true> hands out the pivot pair of every
 //   step, k_coeffs turns them into (rho, 1 / c), k_levinson<E> replays those into x = T^-1 e_0 in double-double, k_diagsums / k_traces
 //   give tr(T^-1 dT_p), k_gs_first / k_gs_second alpha = T^-1 Z by Gohberg-Semencul, k_tprod / k_hdot alpha^T dT_p alpha.
+// The posterior pieces (the comments stand at the kernels): k_pred_sums gives the column sums of squares of
+//   L^-1 K and its products with L^-1 Z in double-double, k_pred_cov (L^-1 K)^T (L^-1 K) on the fp64 MFMA, k_invdiag diag(T^-1) from x.
 // Every value is written with ordinary vector stores; there are no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -541,6 +543,121 @@ __global__ __launch_bounds__(kWave) void k_hdot(const double* __restrict__ As, c
     for (int i = lane; i < n; i += kWave) acc = dd_add(acc, dd_mul_d(dd{q[2 * i], q[2 * i + 1]}, al[i]));
     acc = wave_fold(acc);
     if (lane == 0) h[a * cols + b] = h[b * cols + a] = ldexp(acc.h, ze[set * cols + a] + ze[set * cols + b]);
+}
+
+// ---- the posterior pieces ---------------------------------------------------------------------------------------
+// k_pred_sums and k_pred_cov work on the solved columns Y = L^-1 [K | Z] of one first column: q cross-covariance columns, then c
+// residual columns, (n, q + c) row-major, each scaled by 2^-ze[col] as k_schur loaded it.  k_invdiag works from xd (k_levinson).
+
+// quad[j] = sum_k Y[k, j]^2 (blockIdx.x == 0) and cross[j, b] = sum_k Y[k, j] Y[k, q + b] (blockIdx.x == 1 + b): k_gram's sum in
+// double-double and the house order (lane l takes the rows l, l + 64, ..., then the fold), scaled back by the two exponents.  An
+// output depends on its own two columns and on n alone.  grid = (q, 1 + c), block = kWave.
+__global__ __launch_bounds__(kWave) void k_pred_sums(const double* __restrict__ Y, int n, int q, int c, const int32_t* __restrict__ ze,
+                                                      const int32_t* __restrict__ info, double* __restrict__ quad,
+                                                      double* __restrict__ cross) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const bool is_quad = blockIdx.y == 0;
+    const int b = is_quad ? j : q + (int)blockIdx.y - 1;                      // the other column
+    double* out = is_quad ? quad + j : cross + (int64_t)j * c + (blockIdx.y - 1);
+    if (info[0] != 0) {
+        if (lane == 0) *out = NAN;
+        return;
+    }
+    const int64_t ld = (int64_t)q + c;
+    dd acc = {0.0, 0.0};
+    for (int k = lane; k < n; k += kWave) acc = dd_add(acc, two_prod(Y[k * ld + j], Y[k * ld + b]));
+    acc = wave_fold(acc);
+    if (lane == 0) *out = ldexp(acc.h, ze[j] + ze[b]);
+}
+
+typedef double cov_acc __attribute__((ext_vector_type(4)));
+
+// cov[a, b] = sum_k Y[k, a] Y[k, b], a, b < q, on v_mfma_f64_16x16x4_f64: one wave per 16 x 16 tile on or below the diagonal, the
+// tile above it stored from the same accumulators.  A K step takes four rows of Y: lane l holds Y[k0 + (l >> 4), tile * 16 + (l & 15)]
+// of the row tile as the A operand (A[i][k], i = l & 15) and of the column tile as the B operand (B[k][j], j = l & 15): four
+// contiguous 128-byte segments each, straight from global memory.  In a diagonal tile the two are one fragment, so (i, j) and (j, i)
+// see the same products in the same chain: cov is bitwise symmetric.  The K loop runs 0 .. n in steps of four in every tile, never
+// split; rows beyond n and columns beyond q enter as zeros and are neither read nor written.  The accumulator map is col = lane & 15,
+// row = (lane >> 4) + 4 * reg.  grid = (tiles, tiles), block = kWave; the blocks above the diagonal return at once.
+__global__ __launch_bounds__(kWave) void k_pred_cov(const double* __restrict__ Y, int n, int q, int c, const int32_t* __restrict__ ze,
+                                                     const int32_t* __restrict__ info, double* __restrict__ cov) {
+    const int ti = blockIdx.y, tj = blockIdx.x, lane = threadIdx.x;
+    if (tj > ti) return;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int ca = ti * 16 + fr, cb = tj * 16 + fr;                          // the operand columns this lane loads
+    const bool bad = info[0] != 0;
+    const int64_t ld = (int64_t)q + c;
+    cov_acc acc = {0.0, 0.0, 0.0, 0.0};
+    if (!bad) {
+        const bool diag = ti == tj, ina = ca < q, inb = cb < q;
+        for (int k0 = 0; k0 < n; k0 += 4) {
+            const int k = k0 + fq;
+            const double af = (ina && k < n) ? Y[k * ld + ca] : 0.0;
+            const double bf = diag ? af : ((inb && k < n) ? Y[k * ld + cb] : 0.0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc, 0, 0, 0);
+        }
+    }
+    const int col = tj * 16 + fr;
+    if (col >= q) return;
+    const int ec = ze[col];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = ti * 16 + fq + 4 * r;
+        if (row >= q) continue;
+        const double v = bad ? NAN : ldexp(acc[r], ze[row] + ec);
+        cov[(int64_t)row * q + col] = v;
+        if (ti != tj) cov[(int64_t)col * q + row] = v;
+    }
+}
+
+// p = diag(T^-1) from x = T^-1 e_0 (Gohberg-Semencul): p_i = (1 / x_0) sum_{r <= i} (x_r^2 - x_{n-r}^2), x_n = 0, the term taken as
+// (x_r - x_{n-r}) (x_r + x_{n-r}).  The terms cancel heavily on an ill-conditioned T, so everything up to the one rounding at the end
+// is double-double: thread tid forms its E consecutive terms and their running sums, the threads' totals are scanned through LDS
+// (nine doubling steps, two buffers, an order fixed by the thread count), then the division by x_0.  pd is (m, n); a first column
+// with info != 0 gives NaN.  grid = m, block = kThreads.
+template <int E>
+__global__ __launch_bounds__(kThreads) void k_invdiag(const double* __restrict__ xd, int n, const int32_t* __restrict__ info,
+                                                       double* __restrict__ pd) {
+    __shared__ double s_tot[2][kThreads][2];
+    const int tid = threadIdx.x, base = tid * E;
+    const int64_t theta = blockIdx.x;
+    double* p = pd + theta * n;
+    if (info[theta] != 0) {                                                   // the same in every thread
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (base + e < n) p[base + e] = NAN;
+        return;
+    }
+    const double* x = xd + theta * n * 2;
+    dd run[E];
+    dd acc = {0.0, 0.0};
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int r = base + e;
+        if (r < n) {
+            const dd a = {x[2 * r], x[2 * r + 1]};
+            const dd b = r > 0 ? dd{x[2 * (n - r)], x[2 * (n - r) + 1]} : dd{0.0, 0.0};
+            acc = dd_add(acc, dd_mul(dd_sub(a, b), dd_add(a, b)));
+        }
+        run[e] = acc;
+    }
+    s_tot[0][tid][0] = acc.h;
+    s_tot[0][tid][1] = acc.l;
+    __syncthreads();
+    int cur = 0;
+    for (int off = 1; off < kThreads; off <<= 1) {                            // inclusive scan of the totals
+        dd s = {s_tot[cur][tid][0], s_tot[cur][tid][1]};
+        if (tid >= off) s = dd_add(dd{s_tot[cur][tid - off][0], s_tot[cur][tid - off][1]}, s);
+        s_tot[cur ^ 1][tid][0] = s.h;
+        s_tot[cur ^ 1][tid][1] = s.l;
+        cur ^= 1;
+        __syncthreads();
+    }
+    const dd before = tid > 0 ? dd{s_tot[cur][tid - 1][0], s_tot[cur][tid - 1][1]} : dd{0.0, 0.0};
+    const dd x0 = {x[0], x[1]};
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (base + e < n) p[base + e] = dd_div(dd_add(before, run[e]), x0).h;
 }
 
 }  // namespace gt

@@ -9,8 +9,14 @@ smooth kernels give.
 
 The result is the likelihood of the exactly Toeplitz matrix of ``t``.  ``kernel(X)`` itself is Toeplitz only up to the last bits of its
 entries; on an ill-conditioned matrix that defect, times the condition number, is how far the dense path may sit from this one.
+
+The posterior runs on the same route: the cross-covariance columns of new points ride the forward substitution
+beside the residuals (``toeplitz_predict``), and the inverse's first column gives ``diag(T^-1)`` (``toeplitz_inverse_diagonal``) and
+with it the leave-one-out predictions (``toeplitz_loo``).
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import numpy as np
 
@@ -19,7 +25,7 @@ from ._lib import FAMILY, GSUM_MAX_RHS, KernelDesc
 from .kernels import describe_kernel
 
 __all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n", "toeplitz_inverse_column", "toeplitz_solve",
-           "toeplitz_grad", "toeplitz_gradient_columns"]
+           "toeplitz_grad", "toeplitz_gradient_columns", "ToeplitzPredict", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo"]
 
 
 def uniform_grid_step(X, tol=4.0):
@@ -104,9 +110,33 @@ def _cpu_gram(t, Z, n_sets, steps=None):
     """The device's recursion in numpy: the generator in ``numpy.longdouble``, forward substitution and Gram matrices in fp64.
     ``steps``: a dict that receives what the recursion for the inverse's first column needs (``_cpu_inverse_column``): the reflection
     coefficients ``rho`` and the rotations' ``1 / c`` (m, n - 1) and the last pivot ``L[n-1, n-1]`` (m,), all in long double."""
+    cols = Z.shape[1] // n_sets
+    with np.errstate(all="ignore"):
+        Y, sld, info = _cpu_schur(t, Z, steps)
+        G = _cpu_ordered_gram(Y, n_sets, cols)
+        G[info != 0] = np.nan
+    return G, sld, info
+
+
+def _cpu_ordered_gram(Y, n_sets, cols):
+    """G (m, n_sets, cols, cols) of the solved columns Y (m, n, n_sets * cols) in the device's order (k_gram): 64 partial sums over the
+    rows l, l + 64, ..., then a binary tree over them."""
+    m, n = Y.shape[:2]
+    Yp = np.zeros((m, -(-n // 64) * 64, n_sets, cols))
+    Yp[:, :n] = Y.reshape(m, n, n_sets, cols)
+    Yp = Yp.reshape(m, -1, 64, n_sets, cols)
+    P = np.zeros((m, 64, n_sets, cols, cols))
+    for blk in range(Yp.shape[1]):
+        P += Yp[:, blk, :, :, :, None] * Yp[:, blk, :, :, None, :]
+    while P.shape[1] > 1:
+        P = P[:, 0::2] + P[:, 1::2]
+    return P[:, 0]
+
+
+def _cpu_schur(t, Z, steps=None):
+    """(Y, sum_log_diag, info) of ``_cpu_gram``: the recursion with its forward substitution, Y = L^-1 Z (m, n, ncols) in fp64."""
     ld = np.longdouble
     m, n = t.shape
-    cols = Z.shape[1] // n_sets
     info = np.zeros(m, dtype=np.int32)
     t0 = t[:, 0]
     with np.errstate(all="ignore"):
@@ -150,18 +180,7 @@ def _cpu_gram(t, Z, n_sets, steps=None):
         if steps is not None:
             steps["last"] = u[:, n - 1].copy()
         sld = np.where(good, np.sum(np.log(np.where(good[:, None], diag, 1.0)), axis=1), np.nan)
-        # the device's order (k_gram): 64 partial sums over the rows l, l + 64, ..., then a binary tree over them
-        Yp = np.zeros((m, -(-n // 64) * 64, n_sets, cols))
-        Yp[:, :n] = Y.reshape(m, n, n_sets, cols)
-        Yp = Yp.reshape(m, -1, 64, n_sets, cols)
-        P = np.zeros((m, 64, n_sets, cols, cols))
-        for blk in range(Yp.shape[1]):
-            P += Yp[:, blk, :, :, :, None] * Yp[:, blk, :, :, None, :]
-        while P.shape[1] > 1:
-            P = P[:, 0::2] + P[:, 1::2]
-        G = P[:, 0]
-        G[~good] = np.nan
-    return G, sld, info
+    return Y, sld, info
 
 
 def _first_columns(t):
@@ -399,3 +418,151 @@ def toeplitz_gradient_columns(kernel, X, theta=None, block=256):
         b = min(n, a + block)
         out[:, a:b] = kernel(np.vstack([X[:1], X[a:b]]), eval_gradient=True)[1][1:, 0, :].T
     return out
+
+
+# ---- the posterior pieces ---------------------------------------------------------------------------------------
+
+Y_BUDGET = 256 << 20                                                   # bytes of solved columns one device call of toeplitz_predict keeps
+
+ToeplitzPredict = namedtuple("ToeplitzPredict", ["quad", "cross", "cov", "G", "sum_log_diag", "info"])
+ToeplitzPredict.__doc__ = """What a posterior at q new points takes from T: ``quad`` (q,) = diag(K^T T^-1 K), ``cross`` (q, c) = K^T T^-1 Z,
+``cov`` (q, q) = K^T T^-1 K or None, ``G`` (c, c) = Z^T T^-1 Z, ``sum_log_diag`` and ``info`` as ``toeplitz_gram`` gives them."""
+
+
+def _cpu_predict(t, K, Z, want_cov):
+    """``_cpu_gram``'s recursion on the columns [K | Z], keeping the solved columns Y: quad and cross summed in long double, cov as
+    Y^T Y in fp64 (summed over the rows in order), G in the device's order."""
+    ld = np.longdouble
+    q, c = K.shape[1], Z.shape[1]
+    with np.errstate(all="ignore"):
+        Y, sld, info = _cpu_schur(t[None], np.concatenate([K, Z], axis=1))
+        Y = Y[0]
+        Yk, Yz = Y[:, :q], Y[:, q:]
+        Yl = Yk.astype(ld)
+        quad = np.sum(Yl * Yl, axis=0).astype(float)
+        cross = (Yl.T @ Yz.astype(ld)).astype(float).reshape(q, c)
+        cov = None
+        if want_cov:                                                   # row by row, as the device accumulates it: an entry's sum does not
+            cov = np.zeros((q, q))                                     # depend on the other columns or on their order
+            for k in range(Yk.shape[0]):
+                cov += Yk[k][:, None] * Yk[k][None, :]
+        G = _cpu_ordered_gram(np.ascontiguousarray(Yz)[None], 1, c)[0, 0] if c else np.empty((0, 0))
+        if info[0] != 0:
+            for a in (quad, cross, cov, G):
+                if a is not None:
+                    a[...] = np.nan
+    return quad, cross, cov, G, float(sld[0]), int(info[0])
+
+
+def predict_chunk(n, c=0):
+    """The most new points one device call of ``toeplitz_predict`` takes at order n beside c residual columns: what keeps the solved
+    columns, n (q + c) doubles, within 256 MB."""
+    return max(1, Y_BUDGET // (8 * int(n)) - int(c))
+
+
+def toeplitz_predict(t, K, Z=None, want_cov=False, chunk=None, device=None, backend=None):
+    """``ToeplitzPredict(quad, cross, cov, G, sum_log_diag, info)`` of the symmetric Toeplitz matrix with the first column t, (n,), the
+    cross-covariance columns K, (n, q) -- column j holds the covariances of the n grid points with new point j -- and the residual
+    columns Z, (n, c) with c <= 16, (n,) or None: ``quad[j] = K_j^T T^-1 K_j``, ``cross = K^T T^-1 Z`` (q, c), ``cov = K^T T^-1 K``
+    (q, q; only with ``want_cov``, otherwise None; exactly symmetric) and ``G = Z^T T^-1 Z`` (c, c), bit for bit ``toeplitz_gram``'s.
+    Nothing n x n is formed: the columns ride the forward substitution of the Schur recursion.  ``chunk`` is the largest number of
+    new points per device call (default ``predict_chunk(n, c)``); the results do not depend on it bit for bit.  ``want_cov`` needs all
+    q points in one call: ValueError, naming the limit, otherwise.  Where ``info`` is not 0 every array is NaN."""
+    t = np.asarray(t, dtype=float)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError(f"t must have shape (n,), got {t.shape}")
+    n = t.size
+    K = np.asarray(K, dtype=float)
+    if K.ndim == 1:
+        K = K[:, None]
+    if K.ndim != 2 or K.shape[0] != n or K.shape[1] < 1:
+        raise ValueError(f"K must have shape ({n}, q) with q >= 1, got {K.shape}")
+    Z = np.zeros((n, 0)) if Z is None else np.asarray(Z, dtype=float)
+    if Z.ndim == 1:
+        Z = Z[:, None]
+    if Z.ndim != 2 or Z.shape[0] != n:
+        raise ValueError(f"Z must have shape ({n}, c), got {Z.shape}")
+    q, c = K.shape[1], Z.shape[1]
+    if c > GSUM_MAX_RHS:
+        raise ValueError(f"Z takes at most {GSUM_MAX_RHS} columns, got {c}")
+    limit = predict_chunk(n, c)
+    if chunk is None:
+        chunk = limit
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be >= 1, got {chunk}")
+    if want_cov and q > chunk:
+        raise ValueError(f"want_cov takes all new points in one call: q = {q} exceeds the limit of {chunk} points per call "
+                         f"(n = {n}: {limit} keep the solved columns within {Y_BUDGET >> 20} MB)")
+    if resolve_backend(backend) == "cpu":
+        call = lambda Kc, cov: _cpu_predict(t, Kc, Z, cov)  # noqa: E731
+    else:
+        from . import _toep_lib
+        handle = _toep_lib.default_handle(resolve_device(device))
+        call = lambda Kc, cov: handle.predict(t, Kc, Z, cov)  # noqa: E731
+    if q <= chunk:
+        return ToeplitzPredict(*call(K, want_cov))
+    quad, cross = np.empty(q), np.empty((q, c))
+    for lo in range(0, q, chunk):
+        hi = min(q, lo + chunk)
+        quad[lo:hi], cross[lo:hi], _, G, sld, info = call(K[:, lo:hi], False)
+    return ToeplitzPredict(quad, cross, None, G, sld, info)
+
+
+def _cpu_inverse_diagonal(t):
+    """(p (m, n), info) of ``backend='cpu'``: the long-double running sums of (x_r - x_{n-r}) (x_r + x_{n-r}) over x_0, x the inverse's
+    first column of ``_cpu_pieces`` (whose memo this reuses), rounded to fp64 at the end."""
+    ld = np.longdouble
+    m, n = t.shape
+    _, _, info, _, _, _, _ = _cpu_pieces(t, None, np.zeros((n, 1)), 1, ())
+    x = _cpu_last["x"]
+    with np.errstate(all="ignore"):
+        xn = np.concatenate([np.zeros((m, 1), dtype=ld), x[:, :0:-1]], axis=1)             # x_{n-r}, 0 at r = 0
+        p = (np.cumsum((x - xn) * (x + xn), axis=1) / x[:, :1]).astype(float)
+    p[info != 0] = np.nan
+    return p, info
+
+
+def toeplitz_inverse_diagonal(t, device=None, backend=None):
+    """``(p, info)``: ``p = diag(T^-1)`` of the symmetric Toeplitz matrices with the first columns t, (n,) or (m, n), from the inverse's
+    first column x by Gohberg and Semencul: ``p_i = (1 / x_0) sum_{r <= i} (x_r^2 - x_{n-r}^2)`` with ``x_n = 0``.  The sums cancel
+    heavily on an ill-conditioned T and run in extended precision throughout.  ``info`` as ``toeplitz_inverse_column``; p is NaN where
+    it is not 0."""
+    t2, single = _first_columns(t)
+    if resolve_backend(backend) == "cpu":
+        p, info = _cpu_inverse_diagonal(t2)
+    else:
+        from . import _toep_lib
+        p, _, info = _toep_lib.default_handle(resolve_device(device)).loo(t2, None)
+    return (p[0], int(info[0])) if single else (p, info)
+
+
+def toeplitz_loo(t, y, mean=0.0, device=None, backend=None):
+    """The ``LooResult`` (``gsum_amd.loo``) of the curves y, (n,) or (n, n_curves), under N(mean, T), T the symmetric Toeplitz matrix
+    with the first column t, (n,): ``LooFactor.loo``'s formulas with ``a = T^-1 (y - mean)`` (``toeplitz_solve``) and ``p = diag(T^-1)``
+    (``toeplitz_inverse_diagonal``), both from one recursion; nothing n x n is formed.  ``mean`` is a scalar or (n,).
+    numpy.linalg.LinAlgError where T is not positive definite."""
+    from .loo import LooResult
+    t = np.asarray(t, dtype=float)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError(f"t must have shape (n,), got {t.shape}")
+    n = t.size
+    y = np.asarray(y, dtype=float)
+    if y.ndim not in (1, 2) or y.shape[0] != n or y.size == 0:
+        raise ValueError(f"y must be ({n},) or ({n}, n_curves), got {y.shape}")
+    mean = np.asarray(mean, dtype=float)
+    if mean.shape not in ((), (n,)):
+        raise ValueError(f"mean must be a scalar or ({n},), got {mean.shape}")
+    r = (y.T - mean).T.reshape(n, -1)
+    if resolve_backend(backend) == "cpu":
+        p, info = _cpu_inverse_diagonal(t[None])
+        _, _, _, _, a, _, _ = _cpu_pieces(t[None], None, r, 1, ("alpha",))
+    else:
+        from . import _toep_lib
+        p, a, info = _toep_lib.default_handle(resolve_device(device)).loo(t[None], r)
+    if info[0] != 0:
+        raise np.linalg.LinAlgError("Matrix is not positive definite")
+    p, a = p[0], a[0].reshape(y.shape)
+    pc = p if y.ndim == 1 else p[:, None]
+    return LooResult(mean=y - a / pc, var=1.0 / p, error=a / np.sqrt(pc), logpdf=-0.5 * np.log(2 * np.pi) + 0.5 * np.log(pc) - 0.5 * a * a / pc,
+                     precision_diag=p)

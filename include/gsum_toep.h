@@ -57,6 +57,33 @@
  * gsum_toep_grad_times: ms[0..7] = device milliseconds spent by gsum_toep_grad and gsum_toep_solve in: 0 host-to-device copies, 1 the
  *   Schur recursion, 2 the coefficients and Levinson's recursion, 3 the Gram matrices, 4 the diagonal sums and traces, 5 the
  *   Gohberg-Semencul products (alpha), 6 the Toeplitz products and contractions of H, 7 device-to-host copies.
+ *
+ * The posterior of a process on such a grid needs, for q new points with the cross-covariance columns K (n x q) and the residual
+ * columns Z (n x c), the column sums of squares of L^-1 K, its products with L^-1 Z and, for a predictive covariance, (L^-1 K)^T
+ * (L^-1 K): the substitution of the value path, run on [K | Z], and sums over its solved columns.  Leave-one-out diagnostics need
+ * p = diag(T^-1), which x = T^-1 e_0 gives by Gohberg-Semencul: p_i = (1 / x_0) sum_{r <= i} (x_r^2 - x_{n-r}^2), x_n = 0.
+ *
+ * gsum_toep_predict: one first column t (n).  K is n x q column-major, q >= 1; Z is n x c column-major, 0 <= c <=
+ *   GSUM_TOEP_MAX_COLS (Z, cross_out and G_out may be NULL iff c == 0).  With V = L^-1 K and W = L^-1 Z:
+ *     quad_out[j]     = sum_k V[k, j]^2              = K_j^T T^-1 K_j     (q)
+ *     cross_out[j, b] = sum_k V[k, j] W[k, b]        = K_j^T T^-1 Z_b     (q x c row-major)
+ *     cov_out[a, b]   = sum_k V[k, a] V[k, b]        = K_a^T T^-1 K_b     (q x q, or NULL: not computed; bitwise symmetric)
+ *     G_out           = Z^T T^-1 Z                                        (c x c; bit for bit gsum_toep_gram's for one set)
+ *     sld_out[0], info_out[0] as gsum_toep_gram gives them.  Where info_out[0] != 0 every output is NaN and the call returns 0.
+ *   quad and cross are summed in double-double and rounded once, cov in fp64 on the matrix unit (v_mfma_f64_16x16x4_f64), each in
+ *   an order fixed by n alone: a column's quad and cross are bitwise independent of the other columns, of their order and of q, and
+ *   cov[a, b] depends on the columns a and b and on n alone.  The columns of K are scaled like those of Z, exactly.
+ *   Refused: a null pointer other than those named, q < 1, c outside 0 .. GSUM_TOEP_MAX_COLS, n > gsum_toep_max_n,
+ *   n * (q + c) >= 2^31, cov_out with q > 1048560, a positive finite t[0] outside 2^-64 .. 2^64.  The caller bounds the device
+ *   memory: n * (q + c) doubles of solved columns twice over, and q * q with cov_out.
+ *
+ * gsum_toep_loo: gsum_toep_solve's schedule, and p_out[i] = diag(T_i^-1) (m x n; may not be NULL) from the same x, in double-double
+ *   up to one rounding.  alpha_out (m x n x ncols) is bit for bit gsum_toep_solve's; alpha_out and Z may be NULL together.  info_out
+ *   as gsum_toep_solve; NaN where it is not 0.
+ *
+ * gsum_toep_post_times: ms[0..6] = device milliseconds spent by gsum_toep_predict and gsum_toep_loo in: 0 host-to-device copies, 1 the
+ *   Schur recursion with its substitution, 2 the coefficients and Levinson's recursion, 3 the sums quad, cross and G, 4 cov, 5 the
+ *   inverse's diagonal and the Gohberg-Semencul products, 6 device-to-host copies.  The other two clocks are not charged by them.
  */
 #ifndef GSUM_TOEP_H
 #define GSUM_TOEP_H
@@ -83,6 +110,11 @@ int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, const do
 int gsum_toep_solve(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* x_out, double* alpha_out,
                     int32_t* info_out);
 int gsum_toep_grad_times(gsum_toep* h, double* ms, int32_t reset);
+int gsum_toep_predict(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
+                      double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out);
+int gsum_toep_loo(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* p_out, double* alpha_out,
+                  int32_t* info_out);
+int gsum_toep_post_times(gsum_toep* h, double* ms, int32_t reset);
 
 #ifdef __cplusplus
 }
