@@ -24,7 +24,7 @@ from .graphical import GraphicalDiagnostic
 from .pointwise import TruncationPointwise
 from .loo import FoldResult, LooResult, kfold_from_factor, loo_from_factor, make_folds
 from .toeplitz import (toeplitz_column, toeplitz_grad, toeplitz_gradient_columns, toeplitz_gram, toeplitz_inverse_column, toeplitz_solve,
-                       uniform_grid_step, toeplitz_predict, toeplitz_inverse_diagonal, toeplitz_loo)
+                       uniform_grid_step, toeplitz_predict, toeplitz_inverse_diagonal, toeplitz_loo, toeplitz_panel_width)
 from .stats import hpd, hpd_pdf, median_pdf, cartesian
 from .grid import shard_range, gather_flat, lml_grid_distributed, predict_distributed
 from ._lib import HipContext, HipGroup, KernelDesc, default_context, default_group, device_count, lab_context, load_library
@@ -36,5 +36,5 @@ __all__ = [
     "make_gaussian_partial_sums_uniform", "make_gaussian_partial_sums_on_grid", "sample_mvn_cholesky", "shard_range", "gather_flat",
     "lml_grid_distributed", "Diagnostic", "pivoted_cholesky", "VariogramFourthRoot", "GraphicalDiagnostic", "refdist",
     "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "toeplitz_column", "toeplitz_gram", "uniform_grid_step", "toeplitz_inverse_column", "toeplitz_solve", "toeplitz_grad",
-    "toeplitz_gradient_columns", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
+    "toeplitz_gradient_columns", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo", "toeplitz_panel_width", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
 ]

@@ -29,10 +29,16 @@ PROTOTYPES = {
     "gsum_toep_predict": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_loo": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_post_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_toep_panel_width": (C.c_int32, [_p]),
+    "gsum_toep_gram_panel": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_predict_panel": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_panel_times": (C.c_int, [_p, _dp, C.c_int32]),
 }
 PHASES = ("h2d", "schur", "gram", "d2h")
 GRAD_PHASES = ("h2d", "schur", "levinson", "gram", "diagsums", "solve", "contract", "d2h")    # of grad and solve (gsum_toep_grad_times)
 POST_PHASES = ("h2d", "schur", "levinson", "sums", "cov", "solve", "d2h")                     # of predict and loo (gsum_toep_post_times)
+PANEL_PHASES = ("h2d", "recursion", "diag", "update", "sums", "cov", "d2h")                     # of the panel route (gsum_toep_panel_times)
+METHODS = ("columns", "panel")                                         # the device schedules of gram and predict
 MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
 
 
@@ -48,6 +54,19 @@ def _check(lib, rc):
 def max_n():
     """The largest n ``DeviceToeplitz.gram`` takes (needs no device)."""
     return int(load_library().gsum_toep_max_n(None))
+
+
+def panel_width():
+    """The columns of L per panel on the panel route (needs no device)."""
+    return int(load_library().gsum_toep_panel_width(None))
+
+
+def check_method(method, name="method"):
+    """The one check of ``method=`` / ``toeplitz_method=`` (``name``).  The keyword selects a device schedule, not an arithmetic:
+    ``backend='cpu'`` accepts both values and runs its one code."""
+    if method not in METHODS:
+        raise ValueError(f'{name} must be "columns" or "panel", got {method!r}')
+    return method
 
 
 class DeviceToeplitz(DeviceHandle):
@@ -68,9 +87,10 @@ class DeviceToeplitz(DeviceHandle):
             raise ValueError("the handle is closed")
         return self._h
 
-    def gram(self, t, Z, n_sets):
+    def gram(self, t, Z, n_sets, method="columns"):
         """(G (m, n_sets, c, c), sum_log_diag (m,), info (m,) int32) of the first columns t (m, n) and the right-hand sides Z
-        (n, n_sets * c): gsum_toep_gram."""
+        (n, n_sets * c): gsum_toep_gram, or gsum_toep_gram_panel with ``method="panel"``."""
+        fn = self._lib.gsum_toep_gram_panel if check_method(method) == "panel" else self._lib.gsum_toep_gram
         t = np.ascontiguousarray(t, dtype=np.float64)
         Zf = np.asfortranarray(Z, dtype=np.float64)
         m, n = t.shape
@@ -79,7 +99,7 @@ class DeviceToeplitz(DeviceHandle):
         sld = np.empty(m)
         info = np.empty(m, dtype=np.int32)
         with self._lock:
-            _check(self._lib, self._lib.gsum_toep_gram(self._handle(), _d(t), m, n, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info)))
+            _check(self._lib, fn(self._handle(), _d(t), m, n, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info)))
         return G, sld, info
 
     def grad(self, t, dt, Z, n_sets):
@@ -119,9 +139,11 @@ class DeviceToeplitz(DeviceHandle):
                                                         None if x is None else _d(x), None if alpha is None else _d(alpha), _i32(info)))
         return x, alpha, info
 
-    def predict(self, t, K, Z, want_cov):
+    def predict(self, t, K, Z, want_cov, method="columns"):
         """(quad (q,), cross (q, c), cov (q, q) or None, G (c, c), sum_log_diag, info) of one first column t (n,), the cross-covariance
-        columns K (n, q) and the residual columns Z (n, c), c >= 0: gsum_toep_predict."""
+        columns K (n, q) and the residual columns Z (n, c), c >= 0: gsum_toep_predict, or gsum_toep_predict_panel with
+        ``method="panel"``."""
+        fn = self._lib.gsum_toep_predict_panel if check_method(method) == "panel" else self._lib.gsum_toep_predict
         t = np.ascontiguousarray(t, dtype=np.float64)
         Kf = np.asfortranarray(K, dtype=np.float64)
         Zf = np.asfortranarray(Z, dtype=np.float64)
@@ -131,9 +153,8 @@ class DeviceToeplitz(DeviceHandle):
         sld = np.empty(1)
         info = np.empty(1, dtype=np.int32)
         with self._lock:
-            _check(self._lib, self._lib.gsum_toep_predict(self._handle(), _d(t), n, _d(Kf), q, _d(Zf) if c else None, c, _d(quad),
-                                                          _d(cross) if c else None, None if cov is None else _d(cov), _d(G) if c else None,
-                                                          _d(sld), _i32(info)))
+            _check(self._lib, fn(self._handle(), _d(t), n, _d(Kf), q, _d(Zf) if c else None, c, _d(quad), _d(cross) if c else None,
+                                 None if cov is None else _d(cov), _d(G) if c else None, _d(sld), _i32(info)))
         return quad, cross, cov, G, float(sld[0]), int(info[0])
 
     def loo(self, t, Z):
@@ -152,6 +173,10 @@ class DeviceToeplitz(DeviceHandle):
             _check(self._lib, self._lib.gsum_toep_loo(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, _d(p),
                                                       None if alpha is None else _d(alpha), _i32(info)))
         return p, alpha, info
+
+    def panel_times(self, reset=False):
+        """Device milliseconds spent so far by ``gram`` and ``predict`` with ``method="panel"``, by phase (PANEL_PHASES)."""
+        return self._phase_times("gsum_toep_panel_times", PANEL_PHASES, reset)
 
     def post_times(self, reset=False):
         """Device milliseconds spent so far by ``predict`` and ``loo``, by phase (POST_PHASES)."""

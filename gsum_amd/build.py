@@ -18,7 +18,8 @@
 ``libgsum_toep.so``     the Toeplitz likelihood path (include/gsum_toep.h): the Schur recursion of a symmetric Toeplitz matrix in
                         double-double arithmetic with the forward substitution beside it, the Gram matrices of the solved
                         columns, and the gradient pieces from the first column of the inverse (Levinson's recursion,
-                        Gohberg-Semencul).  Its own small library, built like the variogram's.
+                        Gohberg-Semencul), and the panel route that solves any number of columns from one recursion.  Its own
+                        small library, built like the variogram's.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations

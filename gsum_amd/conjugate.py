@@ -282,6 +282,7 @@ class ConjugateGaussianProcess:
         self.batch_restarts = True   # multi-start fits advance in lock step, objective evaluations batched on the device
         self._fit_structure = None   # "toeplitz" while fit(structure="toeplitz") calibrates
         self.structure_ = None       # "toeplitz" after fit(structure="toeplitz", dense_factor=False): no dense factor is held
+        self._toeplitz_method = "columns"   # the last fit's toeplitz_method=: what predict takes with toeplitz_method=None
         self._ctx = None
         self._L_dev = None          # device-resident Cholesky factor of kernel_(X_train_) + nugget
         self._replicas = {}         # ... and its copies on the other devices of predict(devices=...) (id(context) -> factor)
@@ -524,12 +525,13 @@ class ConjugateGaussianProcess:
     corr_sqrt_ = corr_L_
 
     # -- log marginal likelihood (models.py:912-1039) --------------------------------------------
-    def log_marginal_likelihood(self, theta=None, eval_gradient=False, X=None, y=None, structure=None):
+    def log_marginal_likelihood(self, theta=None, eval_gradient=False, X=None, y=None, structure=None, toeplitz_method="columns"):
         """``structure=None``: the dense route (kernel build, Cholesky, solve).  ``structure="toeplitz"``: the value from the first
         column of the kernel matrix alone (``gsum_amd.toeplitz``; a stationary kernel on a uniform one-dimensional grid, no
-        gradient): the likelihood of the exactly Toeplitz matrix of that column."""
+        gradient): the likelihood of the exactly Toeplitz matrix of that column.  ``toeplitz_method``: ``toeplitz_gram``'s
+        ``method=`` for the value (the gradient stays on the column route)."""
         if structure is not None:
-            return self._lml_structured(structure, [theta], eval_gradient, X, y)[0]
+            return self._lml_structured(structure, [theta], eval_gradient, X, y, toeplitz_method)[0]
         if theta is None and self._fit:
             if eval_gradient:
                 raise ValueError("Gradient can only be evaluated for theta!=None")   # models.py:940-943
@@ -562,7 +564,7 @@ class ConjugateGaussianProcess:
         lml, _ = self._lml_gram(G[0], sld[0], X.shape[0])
         return lml
 
-    def _lml_structured(self, structure, thetas, eval_gradient, X, y):
+    def _lml_structured(self, structure, thetas, eval_gradient, X, y, method="columns"):
         """The values of ``log_marginal_likelihood(theta, structure=...)`` for several theta (None: the fitted / given kernel): one
         first column per theta, one device call for all of them.  Everything the dense route would do silently differently is an error."""
         if structure != "toeplitz":
@@ -571,7 +573,7 @@ class ConjugateGaussianProcess:
             raise NotImplementedError('structure="toeplitz" has no gradient: tr(T^-1 dT) needs the diagonal sums of T^-1')
         from .toeplitz import toeplitz_gram
         X, Z, cols, _ = self._structured_inputs(thetas, X, y)
-        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend)
+        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend, method=method)
         vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
         return np.where(info != 0, -np.inf, vals)                                    # models.py:970-972
 
@@ -673,17 +675,18 @@ class ConjugateGaussianProcess:
             raise ValueError("Unknown optimizer %s." % self.optimizer)
         return theta_opt, func_min
 
-    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None, eval_gradient=False):
+    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None, eval_gradient=False, toeplitz_method="columns"):
         """``log_marginal_likelihood(theta, eval_gradient=True)`` for several ``theta`` at once: [(lml, grad), ...].  The
         evaluations are independent and go to the device as one pipelined batch (gsum_lml_grad_batch); every entry equals
         the single call's result bit for bit.  ``structure="toeplitz"``: the values alone, as an array with one entry per theta
         (``log_marginal_likelihood(theta, structure="toeplitz")``), from one device call; with ``eval_gradient=True`` the dense
-        batch's [(lml, grad), ...] from one device call.  ``eval_gradient`` is read on that route alone."""
+        batch's [(lml, grad), ...] from one device call (DESIGN.md section 19).  ``eval_gradient`` is read on that route alone;
+        ``toeplitz_method`` (``toeplitz_gram``'s ``method=``) on the values alone."""
         if structure is not None:
             thetas = [np.atleast_1d(np.asarray(t, dtype=float)) for t in thetas]
             if eval_gradient:
                 return self._lml_grad_structured(structure, thetas, X, y)
-            return self._lml_structured(structure, thetas, False, X, y)
+            return self._lml_structured(structure, thetas, False, X, y, toeplitz_method)
         self._check_decomposition()
         base = self._active_kernel()
         X = np.asarray(self.X_train_ if X is None else X, dtype=float)
@@ -821,15 +824,19 @@ class ConjugateGaussianProcess:
             return -float(values[best])
         return None
 
-    def fit(self, X, y, structure=None, dense_factor=True):
+    def fit(self, X, y, structure=None, dense_factor=True, toeplitz_method="columns"):
         """``structure="toeplitz"``: every objective evaluation of the calibration -- the single start's and the lock-step restarts' --
         runs on the structured route (``log_marginal_likelihood_batch(.., structure="toeplitz", eval_gradient=True)``); X must be a
         uniform one-dimensional grid and the kernel stationary, checked before the optimiser starts.  The final factorisation, the
         posterior and ``predict`` stay dense, unless ``dense_factor=False`` (with ``structure="toeplitz"`` alone): then the posterior
         attributes come from ``toeplitz_gram`` of the fitted kernel's first column, no n x n matrix is built or factorised,
         ``structure_`` is ``"toeplitz"`` and ``corr_L_`` None, and ``predict``, ``loo`` and ``sample_y`` follow the structured route
-        (DESIGN.md section 20).  ``kfold``, ``predict(devices=...)`` and the 'eig' attributes need the dense factor and say so."""
+        (DESIGN.md section 20).  ``kfold``, ``predict(devices=...)`` and the 'eig' attributes need the dense factor and say so.
+        ``toeplitz_method`` (``toeplitz_predict``'s ``method=``): a fit with ``dense_factor=False`` remembers it for ``predict`` and
+        ``sample_y``; the calibration, with at most one set of columns, stays on the column route."""
         self._check_decomposition()
+        from ._toep_lib import check_method
+        self._toeplitz_method = check_method(toeplitz_method, "toeplitz_method")
         if not dense_factor and structure != "toeplitz":
             raise ValueError('dense_factor=False needs structure="toeplitz": there is no other route without the dense factor')
         if structure is not None:
@@ -1018,7 +1025,8 @@ class ConjugateGaussianProcess:
         return y_mean
 
     # -- predict (models.py:753-845) ------------------------------------------------
-    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, devices=None, structure=None):
+    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, devices=None, structure=None,
+                toeplitz_method=None):
         """``devices`` (additive; ``"all"`` or a list of GPU indices): the new points are cut into one block per device
         (``gsum_shard_range``), every device factorises its own copy of the training matrix once (kept until the next ``fit``) and
         the blocks run side by side, one host thread per device -- columns of the predictive covariance are independent per new
@@ -1029,8 +1037,10 @@ class ConjugateGaussianProcess:
         shifts, the column sums of squares and, with ``return_cov``, (L^-1 K)^T (L^-1 K) -- come from ``toeplitz_predict`` of the
         first column of the conditioning matrix and the cross-covariance columns, which the main library builds; no n x n matrix is
         built or factorised.  The conditioning points (``Xc``, or the training points) must be a uniform one-dimensional grid and
-        the kernel stationary; ``devices=`` is refused.  Everything after the three pieces is the dense route's host algebra."""
-        return self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, False, devices=devices, structure=structure)[0]
+        the kernel stationary; ``devices=`` is refused.  Everything after the three pieces is the dense route's host algebra.
+        ``toeplitz_method``: ``toeplitz_predict``'s ``method=`` on that route; None takes the last fit's."""
+        return self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, False, devices=devices, structure=structure,
+                                  toeplitz_method=toeplitz_method)[0]
 
     def _group(self, devices):
         """The device group of ``devices=`` (process-wide, adopting the default contexts; ``backend='cpu'``: as many CPU contexts)."""
@@ -1054,9 +1064,13 @@ class ConjugateGaussianProcess:
             self._replicas[key] = L
         return L
 
-    def _predict_core(self, X, return_std, return_cov, Xc, y, pred_noise, want_basis, devices=None, structure=None):
+    def _predict_core(self, X, return_std, return_cov, Xc, y, pred_noise, want_basis, devices=None, structure=None, toeplitz_method=None):
         """predict, plus (want_basis) the conditional basis 1 - R_no R^-1 1 of models.py:1168 from the same
-        triangular solve: one more right-hand-side column.  ``structure``: see ``predict``."""
+        triangular solve: one more right-hand-side column.  ``structure``, ``toeplitz_method``: see ``predict``."""
+        if toeplitz_method is None:
+            toeplitz_method = self._toeplitz_method
+        from ._toep_lib import check_method
+        check_method(toeplitz_method, "toeplitz_method")
         if return_std and return_cov:
             raise RuntimeError('Only one of return_std or return_cov may be True')
         if not self._fit:
@@ -1115,7 +1129,8 @@ class ConjugateGaussianProcess:
                 from .toeplitz import toeplitz_predict
                 if resid.shape[1] > GSUM_MAX_RHS:
                     raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS} residual columns, got {resid.shape[1]}')
-                got = toeplitz_predict(t_col, ctx.kernel_matrix(desc, Xc, X), resid, want_cov=return_cov, device=self.device, backend=self.backend)
+                got = toeplitz_predict(t_col, ctx.kernel_matrix(desc, Xc, X), resid, want_cov=return_cov, device=self.device, backend=self.backend,
+                                       method=toeplitz_method)
                 if got.info != 0:
                     raise np.linalg.LinAlgError("Matrix is not positive definite")
                 shifts, colsumsq, VtV = got.cross, got.quad, got.cov
@@ -1241,8 +1256,9 @@ class ConjugateStudentProcess(ConjugateGaussianProcess):
         # corr + basis disp basis^T with the constant basis: an additive constant on top of the kernel
         return cov_factor(scale ** 2, df), describe_kernel(kernel, d).plus_constant(float(np.atleast_2d(disp)[0, 0]))
 
-    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, structure=None):   # models.py:1127-1184
-        pred, basis = self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, True, structure=structure)
+    def predict(self, X, return_std=False, return_cov=False, Xc=None, y=None, pred_noise=False, structure=None,
+                toeplitz_method=None):                                                                              # models.py:1127-1184
+        pred, basis = self._predict_core(X, return_std, return_cov, Xc, y, pred_noise, True, structure=structure, toeplitz_method=toeplitz_method)
         if not self._fit:
             disp = self.disp0
             var = cov_factor(self.scale0 ** 2, self.df0)

@@ -19,16 +19,22 @@ enum Phase { kH2D = 0, kSchur, kGram, kD2H, kPhases };
 enum GradPhase { kGH2D = kPhases, kGSchur, kGLevinson, kGGram, kGDiag, kGSolve, kGContract, kGD2H, kAllPhases };
 // the phases of gsum_toep_predict and gsum_toep_loo (gsum_toep_post_times), after those
 enum PostPhase { kPH2D = kAllPhases, kPSchur, kPLevinson, kPSums, kPCov, kPSolve, kPD2H, kEveryPhase };
+// the phases of gsum_toep_gram_panel and gsum_toep_predict_panel (gsum_toep_panel_times), after those
+enum PanelPhase { kNH2D = kEveryPhase, kNRecursion, kNDiag, kNUpdate, kNSums, kNCov, kND2H, kTotalPhases };
 
 constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y) in flight: the first columns go through in chunks
+// the panel route's: the solved columns with their correction words, the panel and the generator state of the first columns in flight
+constexpr size_t kPanelBudget = (size_t)1 << 30;
 
 }  // namespace
 
-struct gsum_toep : TimedHandle<kEveryPhase> {
+struct gsum_toep : TimedHandle<kTotalPhases> {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
     DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
     DevBuf<double, true> Yz, quad, cross, cov, pd;                             // the posterior's
+    DevBuf<double, true> Ph, Pst;                                              // the panel route's: a panel's high words, the generator state
+    DevBuf<float, true> Pl, Zc;                                                // ... its low words, the correction words beside Y
 };
 
 namespace {
@@ -97,8 +103,8 @@ void read_back(gsum_toep* h, int64_t m, size_t gsz, double* G_out, double* sld_o
 }
 
 // The first columns of one launch: as many as keep `bytes` each within kYBudget, a grid dimension's 65535 at most, one at least.
-int64_t columns_per_launch(int64_t m, size_t bytes) {
-    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(kYBudget / bytes)));
+int64_t columns_per_launch(int64_t m, size_t bytes, size_t budget = kYBudget) {
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(m, 65535), (int64_t)(budget / bytes)));
 }
 
 // What the entry point `who` refuses about the first columns: their order n ...
@@ -220,6 +226,59 @@ void solve_columns(const char* who, const SolvePhases& ph, gsum_toep* h, const d
             SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
         });
     });
+}
+
+// ---- the panel route ----
+
+// Bytes one first column keeps on the device on the panel route: Y with its correction words, one panel, the generator state.
+size_t panel_bytes(int64_t n, int64_t ncols) {
+    size_t ne = 0;
+    with_size_class((int)n, [&](auto k) { ne = (size_t)gt::kThreads * decltype(k)::E; });
+    return (size_t)n * ncols * (sizeof(double) + sizeof(float)) + (size_t)n * gt::kPanelB * (sizeof(double) + sizeof(float)) + 4 * ne * sizeof(double);
+}
+
+// The buffers of `step` first columns in flight on the panel route.
+void reserve_panel(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
+    size_t ne = 0;
+    with_size_class((int)n, [&](auto k) { ne = (size_t)gt::kThreads * decltype(k)::E; });
+    h->Y.reserve((size_t)n * ncols * step);
+    h->Zc.reserve((size_t)n * ncols * step);
+    h->Ph.reserve((size_t)n * gt::kPanelB * step);
+    h->Pl.reserve((size_t)n * gt::kPanelB * step);
+    h->Pst.reserve(4 * ne * step);
+}
+
+// Y = L^-1 Z of cnt first columns t (device) and the ncols columns h->Z / h->ze, with sum_log_diag and info: per panel of kPanelB
+// columns of L the recursion, the triangular block and the trailing update, one after the other on the handle's stream.
+void panel_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+    hipStream_t st = h->stream;
+    timed(h, kNUpdate, [&] {
+        gt::k_panel_load<<<dim3((unsigned)((ncols + 31) / 32), (unsigned)((n + 31) / 32)), dim3(32, 8), 0, st>>>(h->Z.p, h->ze.p, n, ncols, (int)cnt, h->Y.p);
+        SL_LAUNCHED("k_panel_load");
+        SL_CHECK(hipMemsetAsync(h->Zc.p, 0, sizeof(float) * (size_t)n * ncols * cnt, st));
+    });
+    for (int k0 = 0; k0 < n; k0 += gt::kPanelB) {
+        timed(h, kNRecursion, [&] {
+            with_size_class(n, [&](auto k) {
+                using K = decltype(k);
+                gt::k_schur_panel<K::E, K::VL><<<(unsigned)cnt, gt::kThreads, 0, st>>>(t, n, k0, h->Pst.p, h->Ph.p, h->Pl.p, sld, info);
+            });
+            SL_LAUNCHED("k_schur_panel");
+        });
+        timed(h, kNDiag, [&] {
+            const dim3 grid((unsigned)((ncols + gt::kDiagThreads - 1) / gt::kDiagThreads), (unsigned)cnt);
+            gt::k_panel_diag<<<grid, gt::kDiagThreads, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
+            SL_LAUNCHED("k_panel_diag");
+        });
+        const int below = n - k0 - gt::kPanelB;                                // rows under the panel
+        if (below > 0)
+            timed(h, kNUpdate, [&] {
+                const int wide = 16 * gt::kUpdateTiles;
+                const dim3 grid((unsigned)((ncols + wide - 1) / wide), (unsigned)((below + 15) / 16), (unsigned)cnt);
+                gt::k_panel_update<<<grid, gt::kWave, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
+                SL_LAUNCHED("k_panel_update");
+            });
+    }
 }
 
 }  // namespace
@@ -454,5 +513,121 @@ GT_API int gsum_toep_post_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_post_times: null pointer argument");
         read_times(h, kAllPhases, kEveryPhase - kAllPhases, ms, reset);
+    });
+}
+
+GT_API int32_t gsum_toep_panel_width(const gsum_toep*) { return gt::kPanelB; }
+
+GT_API int gsum_toep_gram_panel(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
+                                double* sld_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !Z || !G_out || !sld_out || !info_out) throw Error("gsum_toep_gram_panel: null pointer argument");
+        if (m < 1 || n < 1 || n_sets < 1)
+            throw Error("gsum_toep_gram_panel: m, n and n_sets must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n) + ", " + std::to_string(n_sets));
+        check_cols("gsum_toep_gram_panel", cols);
+        check_order("gsum_toep_gram_panel", n);
+        check_sets("gsum_toep_gram_panel", n, n_sets, cols);
+        check_scale("gsum_toep_gram_panel", t, m, n, " and G and sum_log_diag with it");
+        const int ncols = (int)(n_sets * cols);
+        const size_t per_theta = (size_t)n * ncols;
+        const int64_t step = columns_per_launch(m, panel_bytes(n, ncols), kPanelBudget);
+        const size_t gsz = (size_t)n_sets * cols * cols;
+        run(h, [&] {
+            h->t.reserve((size_t)m * n);
+            h->Z.reserve(per_theta);
+            reserve_panel(h, n, ncols, step);
+            h->G.reserve(gsz * m);
+            h->sld.reserve((size_t)m);
+            h->info.reserve((size_t)m);
+            h->ze.reserve((size_t)ncols);
+            hipStream_t st = h->stream;
+            timed(h, kNH2D, [&] {
+                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
+            });
+            timed(h, kNUpdate, [&] { launch_colexp(h, (int)n, ncols); });
+            for (int64_t lo = 0; lo < m; lo += step) {
+                const int64_t cnt = std::min(step, m - lo);
+                int32_t* il = h->info.p + lo;
+                panel_solve(h, h->t.p + lo * n, (int)n, ncols, cnt, h->sld.p + lo, il);
+                timed(h, kNSums, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
+            }
+            timed(h, kND2H, [&] { read_back(h, m, gsz, G_out, sld_out, info_out); });
+        });
+    });
+}
+
+GT_API int gsum_toep_predict_panel(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c,
+                                   double* quad_out, double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !K || !quad_out || !sld_out || !info_out) throw Error("gsum_toep_predict_panel: null pointer argument");
+        if (q < 1 || n < 1) throw Error("gsum_toep_predict_panel: n and q must be >= 1, got " + std::to_string(n) + ", " + std::to_string(q));
+        if (c < 0 || c > gt::kMaxCols)
+            throw Error("gsum_toep_predict_panel: c must be between 0 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(c));
+        if (c > 0 && (!Z || !cross_out || !G_out)) throw Error("gsum_toep_predict_panel: null pointer argument (Z, cross_out and G_out with c > 0)");
+        check_order("gsum_toep_predict_panel", n);
+        if (q > (((int64_t)1 << 31) - 1) / n - c)
+            throw Error("gsum_toep_predict_panel: n * (q + c) must be < 2^31, got " + std::to_string(n) + " x (" + std::to_string(q) + " + " + std::to_string(c) + ")");
+        if (cov_out && q > 16 * 65535) throw Error("gsum_toep_predict_panel: cov_out takes q <= 1048560, got " + std::to_string(q));
+        check_scale("gsum_toep_predict_panel", t, 1, n, " and the outputs with it");
+        const int ncols = (int)(q + c), qi = (int)q;
+        const size_t ny = (size_t)n * ncols;
+        run(h, [&] {
+            h->t.reserve((size_t)n);
+            h->Z.reserve(ny);
+            reserve_panel(h, n, ncols, 1);
+            h->ze.reserve((size_t)ncols);
+            h->sld.reserve(1);
+            h->info.reserve(1);
+            h->quad.reserve((size_t)q);
+            if (c) {
+                h->cross.reserve((size_t)q * c);
+                h->Yz.reserve((size_t)n * c);
+                h->G.reserve((size_t)c * c);
+            }
+            if (cov_out) h->cov.reserve((size_t)q * q);
+            hipStream_t st = h->stream;
+            timed(h, kNH2D, [&] {
+                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, st));
+                SL_CHECK(hipMemcpyAsync(h->Z.p, K, sizeof(double) * n * q, hipMemcpyHostToDevice, st));
+                if (c) SL_CHECK(hipMemcpyAsync(h->Z.p + (size_t)n * q, Z, sizeof(double) * n * c, hipMemcpyHostToDevice, st));
+            });
+            timed(h, kNUpdate, [&] { launch_colexp(h, (int)n, ncols); });
+            panel_solve(h, h->t.p, (int)n, ncols, 1, h->sld.p, h->info.p);
+            timed(h, kNSums, [&] {
+                gt::k_pred_sums<<<dim3((unsigned)q, (unsigned)(1 + c)), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->quad.p,
+                                                                                          h->cross.p);
+                SL_LAUNCHED("k_pred_sums");
+                if (c) {                                                       // the residual columns alone, as one set of k_gram's
+                    SL_CHECK(hipMemcpy2DAsync(h->Yz.p, sizeof(double) * c, h->Y.p + q, sizeof(double) * ncols, sizeof(double) * c, (size_t)n,
+                                              hipMemcpyDeviceToDevice, st));
+                    gt::k_gram<<<dim3((unsigned)c, 1, 1), gt::kWave, 0, st>>>(h->Yz.p, (int)n, c, 1, h->ze.p + q, h->info.p, h->G.p);
+                    SL_LAUNCHED("k_gram");
+                }
+            });
+            if (cov_out)
+                timed(h, kNCov, [&] {
+                    const unsigned tiles = (unsigned)((q + 15) / 16);
+                    gt::k_pred_cov<<<dim3(tiles, tiles), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->cov.p);
+                    SL_LAUNCHED("k_pred_cov");
+                });
+            timed(h, kND2H, [&] {
+                SL_CHECK(hipMemcpyAsync(quad_out, h->quad.p, sizeof(double) * q, hipMemcpyDeviceToHost, st));
+                if (c) {
+                    SL_CHECK(hipMemcpyAsync(cross_out, h->cross.p, sizeof(double) * q * c, hipMemcpyDeviceToHost, st));
+                    SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * c * c, hipMemcpyDeviceToHost, st));
+                }
+                if (cov_out) SL_CHECK(hipMemcpyAsync(cov_out, h->cov.p, sizeof(double) * q * q, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double), hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            });
+        });
+    });
+}
+
+GT_API int gsum_toep_panel_times(gsum_toep* h, double* ms, int32_t reset) {
+    return guarded([&] {
+        if (!h || !ms) throw Error("gsum_toep_panel_times: null pointer argument");
+        read_times(h, kEveryPhase, kTotalPhases - kEveryPhase, ms, reset);
     });
 }

@@ -25,6 +25,9 @@
 //   give tr(T^-1 dT_p), k_gs_first / k_gs_second alpha = T^-1 Z by Gohberg-Semencul, k_tprod / k_hdot alpha^T dT_p alpha.
 // The posterior pieces (the comments stand at the kernels): k_pred_sums gives the column sums of squares of
 //   L^-1 K and its products with L^-1 Z in double-double, k_pred_cov (L^-1 K)^T (L^-1 K) on the fp64 MFMA, k_invdiag diag(T^-1) from x.
+// The panel route (the comments stand at the kernels): k_schur_panel runs k_schur's step without residual columns
+//   and writes L in panels, k_panel_diag solves a panel's triangular block for every right-hand side, k_panel_update applies the
+//   panel to the rows below on the fp64 MFMA, k_panel_load lays the scaled right-hand sides out row-major.
 // Every value is written with ordinary vector stores; there are no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -658,6 +661,368 @@ __global__ __launch_bounds__(kThreads) void k_invdiag(const double* __restrict__
 #pragma unroll
     for (int e = 0; e < E; ++e)
         if (base + e < n) p[base + e] = dd_div(dd_add(before, run[e]), x0).h;
+}
+
+// ---- the panel route --------------------------------------------------------------------------------------------
+// k_schur's recursion produces the columns of L one after the other and needs none of the right-hand sides; its substitution is an
+// ordinary blocked forward solve that consumes them.  Here the two are separate kernels, and any number of columns ride one recursion:
+// per panel of kPanelB columns of L, k_schur_panel (one workgroup per first column) writes the panel, k_panel_diag solves its
+// triangular block for every column and k_panel_update applies it to the rows below on the fp64 MFMA.  The residuals live in Y itself
+// ((n, ncols) row-major per first column, scaled by k_colexp's exponents by k_panel_load): row k holds the residual z_k until the
+// panel of k is solved and y_k from then on, the fp32 correction words in Zc beside it.  A panel is (kPanelB, n) per first column,
+// column k of L contiguous: Ph the high words, Pl the low words as fp32.  Kernels follow one another in stream order.
+
+#ifndef GSUM_TOEP_PANEL_B
+#define GSUM_TOEP_PANEL_B 64
+#endif
+constexpr int kPanelB = GSUM_TOEP_PANEL_B;         // columns of L per panel: a multiple of 16 (k_panel_diag's blocks, the MFMA's K steps)
+constexpr int kDiagR = 16;                         // rows of a register block of k_panel_diag
+constexpr int kDiagU = 8;                          // later rows of the block it updates at a time
+constexpr int kDiagThreads = 64;                   // columns of a k_panel_diag workgroup
+constexpr int kUpdateTiles = 4;                    // 16-column tiles of a k_panel_update wave
+static_assert(kPanelB % kDiagR == 0 && kPanelB % 4 == 0 && kPanelB >= 16 && kPanelB <= 256, "k_panel_diag and k_panel_update step through a panel in 16s and 4s");
+
+// Y[theta, i, j] = Z[i, j] * 2^-ze[j] for every first column theta < cnt: the column-major right-hand sides into the row-major
+// working residuals, through a 32 x 32 LDS tile.  grid = (ceil(ncols / 32), ceil(n / 32)), block = (32, 8).
+__global__ __launch_bounds__(256) void k_panel_load(const double* __restrict__ Z, const int32_t* __restrict__ ze, int n, int ncols, int cnt,
+                                                     double* __restrict__ Y) {
+    __shared__ double s_t[32][33];
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
+    for (int r = ty; r < 32; r += 8) {                                        // column j0 + r, rows i0 + tx: consecutive in Z
+        const int i = i0 + tx, j = j0 + r;
+        s_t[r][tx] = (i < n && j < ncols) ? ldexp(Z[(int64_t)j * n + i], -ze[j]) : 0.0;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {                                        // row i0 + r, columns j0 + tx: consecutive in Y
+        const int i = i0 + r, j = j0 + tx;
+        if (i < n && j < ncols) {
+            const double v = s_t[tx][r];
+            for (int64_t theta = 0; theta < cnt; ++theta) Y[(theta * n + i) * ncols + j] = v;
+        }
+    }
+}
+
+// k_schur's step without residual columns, for the steps k0 .. min(k0 + kPanelB, n) - 1 of every first column of the launch: the same
+// double-double generator, the same expressions for rho and 1 / c, the same publication through LDS.  The generator state lives in
+// st between launches, (m, 4, kThreads * E): the words u.h, u.l, v.h, v.l of every element; k0 == 0 forms it from t as k_schur does.
+// info[theta] is the running failure step: a first column that has failed is skipped by every later launch.  At step k every thread
+// stores its elements of column k of L (u before the rotation), rows k .. n - 1: Ph[theta, k - k0, i] and (float) of the low word in
+// Pl.  The launch that reaches step n - 1 sums log L_jj from the retained u in k_schur's order, so sum_log_diag and info are bit for
+// bit k_schur's.  grid = m, block = kThreads.
+template <int E, bool VL>
+__global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restrict__ t, int n, int k0, double* __restrict__ st,
+                                                           double* __restrict__ Ph, float* __restrict__ Pl, double* __restrict__ sld,
+                                                           int32_t* __restrict__ info) {
+    __shared__ double s_pub[2][4];
+    __shared__ double s_edge[2][kThreads][2];
+    __shared__ alignas(16) double s_v[VL ? E : 1][VL ? kThreads : 1][2];
+    constexpr int NE = kThreads * E;
+    const int tid = threadIdx.x, base = tid * E;
+    const int64_t theta = blockIdx.x;
+    const double* tt = t + theta * n;
+    double* s = st + theta * 4 * NE;
+    double* ph = Ph + theta * (int64_t)kPanelB * n;
+    float* pl = Pl + theta * (int64_t)kPanelB * n;
+    const int k1 = min(k0 + kPanelB, n);
+
+    int bad;                                                                  // the same in every thread
+    if (k0 == 0) {
+        const double t0 = tt[0];
+        bad = (t0 > 0.0 && t0 < INFINITY) ? 0 : 1;
+    } else {
+        bad = info[theta];
+    }
+    double uh[E], ul[E], vh[VL ? 1 : E], vl[VL ? 1 : E];
+    auto get_v = [&](int e) -> dd { return VL ? dd{s_v[VL ? e : 0][VL ? tid : 0][0], s_v[VL ? e : 0][VL ? tid : 0][1]} : dd{vh[VL ? 0 : e], vl[VL ? 0 : e]}; };
+    auto set_v = [&](int e, dd x) {
+        if (VL) {
+            s_v[VL ? e : 0][VL ? tid : 0][0] = x.h;
+            s_v[VL ? e : 0][VL ? tid : 0][1] = x.l;
+        } else {
+            vh[VL ? 0 : e] = x.h;
+            vl[VL ? 0 : e] = x.l;
+        }
+    };
+    const int b0 = k0 & 1;
+    if (!bad) {
+        dd rs = {0.0, 0.0};
+        if (k0 == 0) rs = dd_rsqrt(dd{tt[0], 0.0});
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int i = base + e;
+            dd u, v;
+            if (k0 == 0) {
+                u = i < n ? dd_mul_d(rs, tt[i]) : dd{0.0, 0.0};
+                v = i > 0 ? u : dd{0.0, 0.0};
+            } else {
+                u = {s[i], s[NE + i]};
+                v = {s[2 * NE + i], s[3 * NE + i]};
+            }
+            uh[e] = u.h;
+            ul[e] = u.l;
+            set_v(e, v);
+            if (i == k0) {
+                s_pub[b0][0] = u.h;
+                s_pub[b0][1] = u.l;
+            }
+            if (i == k0 + 1) {
+                s_pub[b0][2] = v.h;
+                s_pub[b0][3] = v.l;
+            }
+        }
+        s_edge[0][tid][0] = s_edge[1][tid][0] = uh[E - 1];
+        s_edge[0][tid][1] = s_edge[1][tid][1] = ul[E - 1];
+    }
+    __syncthreads();
+
+    for (int k = k0; k < k1 && !bad; ++k) {
+        const int b = k & 1, nb = b ^ 1;
+        const dd pu = {s_pub[b][0], s_pub[b][1]};
+        double* pk = ph + (int64_t)(k - k0) * n;
+        float* qk = pl + (int64_t)(k - k0) * n;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {                                         // column k of L, rows k .. n - 1
+            const int i = base + e;
+            if (i >= k && i < n) {
+                pk[i] = uh[e];
+                qk[i] = (float)ul[e];
+            }
+        }
+        if (k == n - 1) break;
+        const dd rho = dd_div(dd{s_pub[b][2], s_pub[b][3]}, pu);
+        if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every thread
+            bad = k + 2;
+            break;
+        }
+        const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
+        const dd nrho = dd_neg(rho);
+        if (base + E - 1 > k && base < n) {                                  // the thread still holds elements below the pivot
+            dd edge = {0.0, 0.0};
+            if (tid > 0) edge = {s_edge[b][tid - 1][0], s_edge[b][tid - 1][1]};
+#pragma unroll
+            for (int e = E - 1; e >= 0; --e) {
+                const int i = base + e;
+                const dd us = e > 0 ? dd{uh[e > 0 ? e - 1 : 0], ul[e > 0 ? e - 1 : 0]} : edge;      // u shifted down by one
+                const dd v = get_v(e);
+                const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
+                const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+                const bool live = i > k;                                      // at or above the pivot: u[i] keeps L[i, i]
+                uh[e] = live ? un.h : uh[e];
+                ul[e] = live ? un.l : ul[e];
+                set_v(e, vn);
+                if (i == k + 1) {
+                    s_pub[nb][0] = un.h;
+                    s_pub[nb][1] = un.l;
+                }
+                if (i == k + 2) {
+                    s_pub[nb][2] = vn.h;
+                    s_pub[nb][3] = vn.l;
+                }
+            }
+            s_edge[nb][tid][0] = uh[E - 1];
+            s_edge[nb][tid][1] = ul[E - 1];
+        }
+        __syncthreads();
+    }
+
+    if (k1 < n) {                                                             // more panels follow: hand the state on
+        if (!bad) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int i = base + e;
+                const dd v = get_v(e);
+                s[i] = uh[e];
+                s[NE + i] = ul[e];
+                s[2 * NE + i] = v.h;
+                s[3 * NE + i] = v.l;
+            }
+        }
+        if (tid == 0) info[theta] = bad;
+        return;
+    }
+    __syncthreads();
+    double* red = &s_edge[0][0][0];
+    double acc = 0.0;
+    if (!bad) {
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (base + e < n) acc += log(uh[e]);
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
+        if (tid < stride) red[tid] += red[tid + stride];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        sld[theta] = bad ? NAN : red[0];
+        info[theta] = bad;
+    }
+}
+
+// The triangular block of a panel, rows and columns k0 .. k1 - 1 (k1 = min(k0 + kPanelB, n)), for every right-hand-side column: one
+// thread per column, k_schur's substitution literally.  For each k: y_k = (z_k - zc_k) * (1 / hi(L_kk)), then for the rows i of the
+// block below it z_i = fma(-hi(L_ik), y_k, z_i) and zc_i = fmaf(lo(L_ik), (float)y_k, zc_i).  The rows go through the registers 16
+// at a time: the 16 x 16 triangle, then those 16 y applied in ascending k to each later row of the block; the 16 columns of L are
+// staged in LDS for the workgroup (broadcast reads).  Row k of Y receives y_k in place of z_k.
+// grid = (ceil(ncols / kDiagThreads), cnt), block = kDiagThreads.
+__global__ __launch_bounds__(kDiagThreads) void k_panel_diag(const double* __restrict__ Ph, const float* __restrict__ Pl, int n, int k0,
+                                                              int ncols, double* __restrict__ Y, float* __restrict__ Zc,
+                                                              const int32_t* __restrict__ info) {
+    __shared__ double s_h[kDiagR][kPanelB + kDiagU];
+    __shared__ float s_l[kDiagR][kPanelB + kDiagU];
+    const int64_t theta = blockIdx.y;
+    if (info[theta] != 0) return;                                             // the same in every thread
+    const int tid = threadIdx.x, j = blockIdx.x * kDiagThreads + tid;
+    const bool mine = j < ncols;
+    const int kb = min(kPanelB, n - k0);                                      // rows and columns of the block
+    const double* ph = Ph + theta * (int64_t)kPanelB * n;
+    const float* pl = Pl + theta * (int64_t)kPanelB * n;
+    double* y = Y + (theta * n + k0) * ncols + j;                             // row r of the block at y[r * ncols]
+    float* zc = Zc + (theta * n + k0) * ncols + j;
+    for (int s0 = 0; s0 < kb; s0 += kDiagR) {
+        const int nr = min(kDiagR, kb - s0);                                  // rows of this register block
+        __syncthreads();
+        for (int x = tid; x < kDiagR * (kb - s0); x += kDiagThreads) {         // columns s0 .. s0 + nr - 1 of L, rows s0 .. kb - 1 of the block
+            const int c = x / (kb - s0), r = s0 + x % (kb - s0);
+            const bool in = c < nr && r >= s0 + c;                            // on or below the diagonal: what k_schur_panel stored
+            s_h[c][r] = in ? ph[(int64_t)(s0 + c) * n + k0 + r] : 0.0;
+            s_l[c][r] = in ? pl[(int64_t)(s0 + c) * n + k0 + r] : 0.f;
+        }
+        __syncthreads();
+        if (!mine) continue;
+        double z[kDiagR], yk[kDiagR];
+        float c32[kDiagR], yf[kDiagR];
+#pragma unroll
+        for (int r = 0; r < kDiagR; ++r) {
+            z[r] = r < nr ? y[(int64_t)(s0 + r) * ncols] : 0.0;
+            c32[r] = r < nr ? zc[(int64_t)(s0 + r) * ncols] : 0.f;
+        }
+#pragma unroll
+        for (int c = 0; c < kDiagR; ++c) {
+            yk[c] = 0.0;
+            yf[c] = 0.f;
+            if (c < nr) {
+                yk[c] = (z[c] - (double)c32[c]) * (1.0 / s_h[c][s0 + c]);
+                yf[c] = (float)yk[c];
+#pragma unroll
+                for (int r = c + 1; r < kDiagR; ++r) {
+                    if (r < nr) {
+                        z[r] = fma(-s_h[c][s0 + r], yk[c], z[r]);
+                        c32[r] = fmaf(s_l[c][s0 + r], yf[c], c32[r]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kDiagR; ++r)
+            if (r < nr) y[(int64_t)(s0 + r) * ncols] = yk[r];
+        for (int r = s0 + kDiagR; r < kb; r += kDiagU) {                       // the later rows of the block, kDiagU loads in flight
+            double zr[kDiagU];
+            float cr[kDiagU];
+#pragma unroll
+            for (int u = 0; u < kDiagU; ++u) {
+                zr[u] = r + u < kb ? y[(int64_t)(r + u) * ncols] : 0.0;
+                cr[u] = r + u < kb ? zc[(int64_t)(r + u) * ncols] : 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < kDiagR; ++c) {
+#pragma unroll
+                for (int u = 0; u < kDiagU; ++u) {     // rows beyond kb: whatever the padding holds (never written), and not stored
+                    zr[u] = fma(-s_h[c][r + u], yk[c], zr[u]);
+                    cr[u] = fmaf(s_l[c][r + u], yf[c], cr[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kDiagU; ++u) {
+                if (r + u < kb) {
+                    y[(int64_t)(r + u) * ncols] = zr[u];
+                    zc[(int64_t)(r + u) * ncols] = cr[u];
+                }
+            }
+        }
+    }
+}
+
+// The trailing update of a full panel (k0 + kPanelB < n) on v_mfma_f64_16x16x4_f64: for the rows i >= k0 + kPanelB,
+// Z[i, j] -= sum_k hi(L_ik) Y[k, j] over the panel's columns k in ascending order.  One wave per 16 rows and kUpdateTiles 16-column
+// tiles: the residual tile is the accumulator (col = lane & 15, row = (lane >> 4) + 4 * reg, as in k_pred_cov), lane l holds
+// -L[r0 + (l & 15), k0 + 4 s + (l >> 4)] as the A operand of K step s (16 contiguous doubles of a column of L per quarter wave) and
+// Y[k0 + 4 s + (l >> 4), c0 + (l & 15)] as the B operand, straight from global memory.  The K loop is never split, so an entry sees
+// one chain in one order, fixed by n and kPanelB alone.  The correction word takes zc[i, j] += lo(L_ik) * (float)y_k for the same k
+// in ascending order on the vector unit (k_schur's fmaf chain), its factors shuffled out of the operand fragments.  Rows beyond n
+// and columns beyond ncols enter as zeros and are neither read nor written.
+// grid = (ceil(ncols / 64), ceil((n - k0 - kPanelB) / 16), cnt), block = kWave.
+__global__ __launch_bounds__(kWave) void k_panel_update(const double* __restrict__ Ph, const float* __restrict__ Pl, int n, int k0, int ncols,
+                                                         double* __restrict__ Y, float* __restrict__ Zc, const int32_t* __restrict__ info) {
+    const int64_t theta = blockIdx.z;
+    if (info[theta] != 0) return;
+    const int lane = threadIdx.x, fr = lane & 15, fq = lane >> 4;
+    const int r0 = k0 + kPanelB + blockIdx.y * 16;
+    const int c0 = blockIdx.x * (16 * kUpdateTiles);
+    const double* ph = Ph + theta * (int64_t)kPanelB * n;
+    const float* pl = Pl + theta * (int64_t)kPanelB * n;
+    double* Yt = Y + theta * (int64_t)n * ncols;
+    float* Ct = Zc + theta * (int64_t)n * ncols;
+    const int arow = r0 + fr;                                                 // the row of L this lane loads as the A operand
+    const bool ina = arow < n;
+    cov_acc acc[kUpdateTiles];
+    float zc[kUpdateTiles][4];
+#pragma unroll
+    for (int t = 0; t < kUpdateTiles; ++t) {
+        const int col = c0 + 16 * t + fr;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = r0 + fq + 4 * r;
+            const bool in = row < n && col < ncols;
+            acc[t][r] = in ? Yt[(int64_t)row * ncols + col] : 0.0;
+            zc[t][r] = in ? Ct[(int64_t)row * ncols + col] : 0.f;
+        }
+    }
+#pragma unroll 2
+    for (int s = 0; s < kPanelB / 4; ++s) {
+        const int k = 4 * s + fq;
+        const double af = ina ? -ph[(int64_t)k * n + arow] : 0.0;
+        const float alf = ina ? pl[(int64_t)k * n + arow] : 0.f;             // the low word of the same entry of L
+        float bff[kUpdateTiles];
+#pragma unroll
+        for (int t = 0; t < kUpdateTiles; ++t) {
+            bff[t] = 0.f;
+            if (c0 + 16 * t >= ncols) continue;                               // the same in every lane
+            const int col = c0 + 16 * t + fr;
+            const double bf = col < ncols ? Yt[(int64_t)(k0 + k) * ncols + col] : 0.0;
+            bff[t] = (float)bf;
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af, bf, acc[t], 0, 0, 0);
+        }
+        // the correction words of the four columns k0 + 4 s + kk in ascending order: lo(L) of the lane's rows and (float)y of its
+        // columns are in the operand fragments of the quarter wave kk, taken from there with lane shuffles
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            float lo[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lo[r] = __shfl(alf, kk * 16 + fq + 4 * r, kWave);
+#pragma unroll
+            for (int t = 0; t < kUpdateTiles; ++t) {
+                if (c0 + 16 * t >= ncols) continue;
+                const float yf = __shfl(bff[t], kk * 16 + fr, kWave);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) zc[t][r] = fmaf(lo[r], yf, zc[t][r]);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < kUpdateTiles; ++t) {
+        const int col = c0 + 16 * t + fr;
+        if (col >= ncols) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = r0 + fq + 4 * r;
+            if (row >= n) continue;
+            Yt[(int64_t)row * ncols + col] = acc[t][r];
+            Ct[(int64_t)row * ncols + col] = zc[t][r];
+        }
+    }
 }
 
 }  // namespace gt

@@ -22,9 +22,10 @@ import numpy as np
 
 from ._backend import resolve_backend, resolve_device
 from ._lib import FAMILY, GSUM_MAX_RHS, KernelDesc
+from ._toep_lib import check_method
 from .kernels import describe_kernel
 
-__all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n", "toeplitz_inverse_column", "toeplitz_solve",
+__all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n", "toeplitz_panel_width", "toeplitz_inverse_column", "toeplitz_solve",
            "toeplitz_grad", "toeplitz_gradient_columns", "ToeplitzPredict", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo"]
 
 
@@ -206,21 +207,33 @@ def _rhs_sets(Z, n, n_sets):
     return Z, n_sets, cols
 
 
-def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None):
+def toeplitz_panel_width():
+    """The columns of L per panel of ``method="panel"`` on the device (needs no device): a compile-time constant of the library."""
+    from . import _toep_lib
+    return _toep_lib.panel_width()
+
+
+def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None, method="columns"):
     """``(G, sum_log_diag, info)`` of the symmetric Toeplitz matrices with the first columns t, (n,) or (m, n), and the right-hand sides
     Z, (n, n_sets * c) in ``n_sets`` sets of c <= 16 columns: ``G[s] = Z_s^T T^-1 Z_s`` (c x c), ``sum_log_diag = sum_j log L_jj`` of
     ``T = L L^T`` and ``info`` = 0, or the 1-based step at which the pivot of the recursion stops being finite and positive (then G and
     sum_log_diag are NaN).  Shapes: t (n,) gives G (n_sets, c, c) and two scalars; t (m, n) gives (m, n_sets, c, c), (m,), (m,).
     ValueError beyond ``toeplitz_max_n()`` on the device: nothing falls back to a dense evaluation.  On the device the scale of Z is
     free (each column is normalised by a power of two and G scaled back, both exactly), while a positive finite ``t[0]`` outside
-    2^-64 .. 2^64 is a ValueError: scale t by a power of 4 instead."""
+    2^-64 .. 2^64 is a ValueError: scale t by a power of 4 instead.
+    ``method="columns"`` keeps the residual columns beside the recursion, a few per workgroup, and repeats the recursion for every
+    further few; ``method="panel"`` runs one recursion per first column in panels of
+    ``toeplitz_panel_width()`` columns of L and applies each panel to all columns at once on the matrix unit: the schedule for many
+    sets.  Same arithmetic per entry, cut into panels: G agrees to the accuracy of either, ``sum_log_diag`` and ``info`` bit for
+    bit.  ``backend='cpu'`` has one code for both."""
+    check_method(method)
     t2, single = _first_columns(t)
     Z, n_sets, cols = _rhs_sets(Z, t2.shape[1], n_sets)
     if resolve_backend(backend) == "cpu":
         G, sld, info = _cpu_gram(t2, Z, n_sets)
     else:
         from . import _toep_lib
-        G, sld, info = _toep_lib.default_handle(resolve_device(device)).gram(t2, Z, n_sets)
+        G, sld, info = _toep_lib.default_handle(resolve_device(device)).gram(t2, Z, n_sets, method)
     if single:
         return G[0], float(sld[0]), int(info[0])
     return G, sld, info
@@ -460,14 +473,16 @@ def predict_chunk(n, c=0):
     return max(1, Y_BUDGET // (8 * int(n)) - int(c))
 
 
-def toeplitz_predict(t, K, Z=None, want_cov=False, chunk=None, device=None, backend=None):
+def toeplitz_predict(t, K, Z=None, want_cov=False, chunk=None, device=None, backend=None, method="columns"):
     """``ToeplitzPredict(quad, cross, cov, G, sum_log_diag, info)`` of the symmetric Toeplitz matrix with the first column t, (n,), the
     cross-covariance columns K, (n, q) -- column j holds the covariances of the n grid points with new point j -- and the residual
     columns Z, (n, c) with c <= 16, (n,) or None: ``quad[j] = K_j^T T^-1 K_j``, ``cross = K^T T^-1 Z`` (q, c), ``cov = K^T T^-1 K``
     (q, q; only with ``want_cov``, otherwise None; exactly symmetric) and ``G = Z^T T^-1 Z`` (c, c), bit for bit ``toeplitz_gram``'s.
     Nothing n x n is formed: the columns ride the forward substitution of the Schur recursion.  ``chunk`` is the largest number of
     new points per device call (default ``predict_chunk(n, c)``); the results do not depend on it bit for bit.  ``want_cov`` needs all
-    q points in one call: ValueError, naming the limit, otherwise.  Where ``info`` is not 0 every array is NaN."""
+    q points in one call: ValueError, naming the limit, otherwise.  Where ``info`` is not 0 every array is NaN.
+    ``method="panel"``: all columns of a call ride one recursion (``toeplitz_gram``); ``chunk`` then only bounds the memory."""
+    check_method(method)
     t = np.asarray(t, dtype=float)
     if t.ndim != 1 or t.size < 1:
         raise ValueError(f"t must have shape (n,), got {t.shape}")
@@ -499,7 +514,7 @@ def toeplitz_predict(t, K, Z=None, want_cov=False, chunk=None, device=None, back
     else:
         from . import _toep_lib
         handle = _toep_lib.default_handle(resolve_device(device))
-        call = lambda Kc, cov: handle.predict(t, Kc, Z, cov)  # noqa: E731
+        call = lambda Kc, cov: handle.predict(t, Kc, Z, cov, method)  # noqa: E731
     if q <= chunk:
         return ToeplitzPredict(*call(K, want_cov))
     quad, cross = np.empty(q), np.empty((q, c))

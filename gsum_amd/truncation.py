@@ -291,7 +291,7 @@ class TruncationGP:
         return coeff_log_like - det_factor
 
     def log_marginal_likelihood_grid(self, thetas, ratio_kws_list, scales=None, X=None, y=None, orders=None, mode="full",
-                                     shard=None, devices=None, gather="host", _ctx=None, structure=None):
+                                     shard=None, devices=None, gather="host", _ctx=None, structure=None, toeplitz_method="columns"):
         """Likelihood surface over (ratio settings) x (thetas) [x (prior scales)].
 
         ``scales=None``: ``out[i, j]`` equals ``self.log_marginal_likelihood(thetas[j], **ratio_kws_list[i])``.
@@ -319,13 +319,15 @@ class TruncationGP:
         recursion per theta with every ratio setting as a set of right-hand sides, O(n^2) per point and no n x n matrix.  It is the
         likelihood of the exactly Toeplitz matrix of that column; both modes give the same numbers, ``shard`` splits whole thetas, and
         ``devices=`` / ``gather=``, more than 15 curves, a non-uniform X and a non-stationary kernel are errors, never a dense evaluation.
+        ``toeplitz_method="panel"`` (``toeplitz_gram``'s ``method=``): all ratio settings ride one recursion per
+        theta instead of one per few columns.
         """
         if structure is not None:
             if structure != "toeplitz":
                 raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
             if devices is not None or gather != "host" or _ctx is not None:
                 raise ValueError('structure="toeplitz" runs on one device: devices= and gather= are not supported (shard= is)')
-            return self._grid_toeplitz(thetas, ratio_kws_list, scales, X, y, orders, mode, shard)
+            return self._grid_toeplitz(thetas, ratio_kws_list, scales, X, y, orders, mode, shard, toeplitz_method)
         if devices is not None:
             if shard is not None:
                 raise ValueError("shard= (one process per GPU) and devices= (one process, several GPUs) exclude each other")
@@ -479,7 +481,7 @@ class TruncationGP:
         return shaped(out)
 
 
-    def _grid_toeplitz(self, thetas, ratio_kws_list, scales, X, y, orders, mode, shard):
+    def _grid_toeplitz(self, thetas, ratio_kws_list, scales, X, y, orders, mode, shard, method="columns"):
         """The surface of ``structure="toeplitz"``: one first column per theta of this rank, one set [coefficients | 1] per ratio
         setting, one device call; the prior scales only enter the host algebra."""
         from .grid import owned_points
@@ -514,7 +516,7 @@ class TruncationGP:
             cols = np.stack([column_of_desc(ctx, d, Xd, gp.nugget) for d in descs])
             Zs, dets = self._rhs_rows(Xd, y, orders, [kws if isinstance(kws, dict) else {"ratio": kws} for kws in ratio_kws_list])
             k = Zs.shape[2]
-            G, sld, info = toeplitz_gram(cols, Zs.transpose(1, 0, 2).reshape(n_pts, ni * k), ni, device=gp.device, backend=gp.backend)
+            G, sld, info = toeplitz_gram(cols, Zs.transpose(1, 0, 2).reshape(n_pts, ni * k), ni, device=gp.device, backend=gp.backend, method=method)
             # (thetas, rows, scales) entries of the host algebra
             Gb = np.broadcast_to(G[:, :, None], (len(js), ni, ns, k, k)).reshape(-1, k, k)
             sb = np.broadcast_to(sld[:, None, None], (len(js), ni, ns)).reshape(-1)

@@ -84,6 +84,30 @@
  * gsum_toep_post_times: ms[0..6] = device milliseconds spent by gsum_toep_predict and gsum_toep_loo in: 0 host-to-device copies, 1 the
  *   Schur recursion with its substitution, 2 the coefficients and Levinson's recursion, 3 the sums quad, cross and G, 4 cov, 5 the
  *   inverse's diagonal and the Gohberg-Semencul products, 6 device-to-host copies.  The other two clocks are not charged by them.
+ *
+ * The panel route (opt-in; the entry points above are unchanged).  gsum_toep_gram and gsum_toep_predict keep the residuals of a few
+ * right-hand sides (16, 12, 5 or 3, by n) in the registers of the workgroup that runs the recursion, and every further few columns
+ * cost a second, identical recursion in another workgroup.  The recursion needs none of the columns: the entry points below run it
+ * once per first column, in panels of B = gsum_toep_panel_width() columns of L, and solve all right-hand sides against each panel:
+ * the B x B triangular block by the substitution of the entry points above, literally (y_k = (z_k - zc_k) (1 / hi(L_kk)), an fp64
+ * FMA chain with the high words of L, the low words summed in an fp32 word beside each residual), the rows below the panel by a
+ * trailing update on the matrix unit (v_mfma_f64_16x16x4_f64, the panel's columns in ascending order, never split).  Nothing n x n
+ * is stored: one panel (n x B, 12 bytes an entry) per first column in flight.  The per-entry arithmetic is that of the column
+ * entry points cut into panels; the results agree with theirs to the accuracy of either, not bit for bit in general;
+ * sum_log_diag and info are bit for bit theirs.  A (first column, right-hand side) result is bitwise reproducible and does not
+ * depend on the other columns, on their order or number, on m or on how the first columns are chunked.
+ *
+ * gsum_toep_panel_width: B, a compile-time constant of the library.  h may be NULL.
+ *
+ * gsum_toep_gram_panel: the arguments, outputs and refusals of gsum_toep_gram.  All n_sets * cols columns ride one recursion per
+ *   first column; the first columns go through in chunks that keep their solved columns, panels and generator states within 1 GiB.
+ *
+ * gsum_toep_predict_panel: the arguments, outputs and refusals of gsum_toep_predict; [K | Z] rides one recursion.  G_out agrees with
+ *   gsum_toep_gram_panel's for one set bit for bit.
+ *
+ * gsum_toep_panel_times: ms[0..6] = device milliseconds spent by the two in: 0 host-to-device copies, 1 the recursion, 2 the
+ *   triangular blocks, 3 the trailing updates (with the scaling of the right-hand sides), 4 the sums G, quad and cross, 5 cov,
+ *   6 device-to-host copies.  The other three clocks are not charged by them.
  */
 #ifndef GSUM_TOEP_H
 #define GSUM_TOEP_H
@@ -115,6 +139,12 @@ int gsum_toep_predict(gsum_toep* h, const double* t, int64_t n, const double* K,
 int gsum_toep_loo(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* p_out, double* alpha_out,
                   int32_t* info_out);
 int gsum_toep_post_times(gsum_toep* h, double* ms, int32_t reset);
+int32_t gsum_toep_panel_width(const gsum_toep* h);
+int gsum_toep_gram_panel(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
+                         double* sld_out, int32_t* info_out);
+int gsum_toep_predict_panel(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
+                            double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out);
+int gsum_toep_panel_times(gsum_toep* h, double* ms, int32_t reset);
 
 #ifdef __cplusplus
 }
