@@ -114,6 +114,8 @@ class CpuMatrix:
         self.n = self.A.shape[0]
         self.factored = False
         self.pivoted = False
+        self.failed = False         # consumed by a failed factorisation (info > 0): only to_host and free take it, as on the device
+        self.solved_W = None        # W = L^-1 rhs of the last forward_gram / forward_solve / predict_terms(rhs=...): gsum_mat's solved_k
         self.piv = None
 
     def to_host(self):
@@ -121,6 +123,7 @@ class CpuMatrix:
 
     def scale_series(self, series, ref, ratio):
         """A_ij *= factor ref_i ref_j S(ratio_i ratio_j)  (TruncationProcess.cov, gsum/models.py:1343-1354)."""
+        _refuse_failed(self, "scale_series")
         if self.factored:
             raise ValueError("scale_series needs an unfactored matrix")
         ref, ratio = np.asarray(ref, dtype=float), np.asarray(ratio, dtype=float)
@@ -128,6 +131,33 @@ class CpuMatrix:
 
     def free(self):
         self.A = None
+
+
+def _refuse_failed(M, call):
+    if M.failed:
+        raise ValueError(f"{call}: the matrix was consumed by a failed factorisation (info > 0); upload or build it again")
+
+
+def _need_factor(L, call):
+    """The device library's gs_need_factor: an unpivoted Cholesky factor, or ValueError (include/gsum_hip.h's state contract)."""
+    _refuse_failed(L, call)
+    if not L.factored:
+        raise ValueError(f"{call} needs a factorised matrix")
+    if L.pivoted:
+        raise ValueError(f"{call}: the matrix holds a pivoted factor (of P^T A P, in pivot order); only sqrt_errors with pivot = 1 takes it")
+
+
+def _rhs(L, a, call, one_call):
+    """a as (n, k) float64 with the factor's row count -- and, where the device runs ONE call on it, 1 <= k <= GSUM_MAX_RHS."""
+    a = np.asarray(a, dtype=float)
+    squeeze = a.ndim == 1
+    if squeeze:
+        a = a[:, None]
+    if a.shape[0] != L.n:
+        raise ValueError(f"{call}: the right-hand sides have the wrong number of rows")
+    if one_call and not 1 <= a.shape[1] <= GSUM_MAX_RHS:
+        raise ValueError("k must be 1..GSUM_MAX_RHS")
+    return a, squeeze
 
 
 def _series_factor(series, ref_r, ratio_r, ref_c, ratio_c):
@@ -189,22 +219,26 @@ class CpuContext:
     def potrf(self, M: CpuMatrix) -> int:
         """numpy.linalg.cholesky's LAPACK call with its info (0 = success, k > 0: leading minor k is not positive definite)."""
         self.calls["potrf"] += 1
+        _refuse_failed(M, "potrf")
         if M.factored:
             raise ValueError("matrix is already factorised")
         c, info = dpotrf(M.A, lower=1, clean=1, overwrite_a=0)
         if info == 0:
             M.A = c
-            M.factored = True
+            M.factored, M.pivoted = True, False
+        M.failed = info > 0
         return int(info)
 
     def pstrf(self, M: CpuMatrix):
         """gsum_sqrt_errors' pivoted factorisation: LAPACK dpstrf (lower, tol -1) -> (info, piv); info 0 or rank + 1, piv 0-based."""
         self.calls["pstrf"] += 1
+        _refuse_failed(M, "pstrf")
         if M.factored:
             raise ValueError("matrix is already factorised")
         c, piv, rank, info = dpstrf(M.A, tol=-1.0, lower=1)
         piv = np.asarray(piv, dtype=np.int64) - 1
         if info != 0:
+            M.failed = True
             return int(rank) + 1, piv
         M.A, M.factored, M.pivoted, M.piv = np.tril(c), True, True, piv
         return 0, piv
@@ -212,13 +246,16 @@ class CpuContext:
     def sqrt_errors(self, L: CpuMatrix, Y, mean=None, pivot=False, errors=True, md2=False):
         """gsum_sqrt_errors: E = L^-1 P^T (Y - mean 1^T), md2_j = sum_i E_ij^2 (an unfactored L is factorised first)."""
         self.calls["sqrt_errors"] += 1
+        _refuse_failed(L, "sqrt_errors")
+        Y = np.asarray(Y, dtype=float)
+        if Y.shape[0] != L.n:
+            raise ValueError(f"Y has {Y.shape[0]} rows, the factor {L.n}")
         if not L.factored:
             info = self.pstrf(L)[0] if pivot else self.potrf(L)
             if info:
                 raise np.linalg.LinAlgError(f"{'pstrf' if pivot else 'potrf'}: matrix is not positive definite (info {info})")
         elif bool(L.pivoted) != bool(pivot):
             raise ValueError("sqrt_errors: the matrix holds a " + ("pivoted" if L.pivoted else "unpivoted") + " factor")
-        Y = np.asarray(Y, dtype=float)
         R = Y if mean is None else (Y.T - np.asarray(mean, dtype=float)).T
         if pivot:
             R = R[L.piv]
@@ -232,22 +269,25 @@ class CpuContext:
         return K, self.potrf(K)
 
     def forward_solve(self, L: CpuMatrix, rhs):
-        rhs = np.asarray(rhs, dtype=float)
-        return solve_triangular(L.A, rhs, lower=True)
+        _need_factor(L, "forward_solve")
+        rhs, squeeze = _rhs(L, rhs, "forward_solve", True)
+        W = solve_triangular(L.A, rhs, lower=True)
+        L.solved_W = W                              # (what the device factor's border rows hold: gsum_predict_var reads it)
+        return W[:, 0] if squeeze else W
 
     def forward_gram(self, L: CpuMatrix, rhs):
         self.calls["forward_gram"] += 1
-        rhs = np.asarray(rhs, dtype=float)
-        if rhs.ndim == 1:
-            rhs = rhs[:, None]
+        _need_factor(L, "forward_gram")
+        rhs, _ = _rhs(L, rhs, "forward_gram", True)
         W = solve_triangular(L.A, rhs, lower=True)
-        L.solved_W = W                              # (what the device factor's border rows hold: gsum_predict_var reads it)
+        L.solved_W = W
         return W.T @ W, float(np.log(np.diag(L.A)).sum())
 
     def predict_var(self, L: CpuMatrix, desc, X, Xs, want_vtw=False):
         """gsum_predict_var's contract: column sums of squares of V = L^-1 kernel(X, Xs) and, with ``want_vtw``, V^T W as m x GSUM_MAX_RHS
         (columns beyond the k held right-hand sides zero) for the right-hand sides of the last forward_gram on this factor."""
-        W = getattr(L, "solved_W", None)
+        _need_factor(L, "predict_var")
+        W = L.solved_W
         if want_vtw and W is None:
             raise ValueError("gsum_predict_var: V^T W needs right-hand sides solved against this factor first (gsum_forward_gram)")
         V = solve_triangular(L.A, kernel_matrix(desc, np.asarray(X, dtype=float), np.asarray(Xs, dtype=float)), lower=True)
@@ -259,14 +299,25 @@ class CpuContext:
         return css, out
 
     def cho_solve(self, L: CpuMatrix, B):
-        return _cho_solve((L.A, True), np.asarray(B, dtype=float))
+        _need_factor(L, "cho_solve")
+        B, squeeze = _rhs(L, B, "cho_solve", False)
+        if B.shape[1]:
+            L.solved_W = None                       # (the device's back-substitution overwrites the border rows in place)
+        X = _cho_solve((L.A, True), B)
+        return X[:, 0] if squeeze else X
 
     def tri_multiply(self, L: CpuMatrix, Z):
-        return np.tril(L.A) @ np.asarray(Z, dtype=float)
+        _need_factor(L, "tri_multiply")
+        Z, squeeze = _rhs(L, Z, "tri_multiply", False)
+        out = np.tril(L.A) @ Z
+        return out[:, 0] if squeeze else out
 
     def predict_terms(self, L: CpuMatrix, desc, X, Xs, rhs=None, want_cov=False, series=None):
         self.calls["predict_terms"] += 1
+        _need_factor(L, "predict_terms")
         X, Xs = np.asarray(X, dtype=float), np.asarray(Xs, dtype=float)
+        if X.shape[0] != L.n or Xs.shape[0] <= 0:
+            raise ValueError("bad shapes")
         Kon = kernel_matrix(desc, X, Xs)                             # n x m, two-argument form: no white noise
         if series is not None:
             sc, ref_x, ratio_x, ref_s, ratio_s = series
@@ -279,7 +330,12 @@ class CpuContext:
             rhs = np.asarray(rhs, dtype=float)
             if rhs.ndim == 1:
                 rhs = rhs[:, None]
-            VtW = V.T @ solve_triangular(L.A, rhs, lower=True)
+            if rhs.shape[0] != L.n or rhs.shape[1] > GSUM_MAX_RHS:
+                raise ValueError("bad RHS / k")
+            W = solve_triangular(L.A, rhs, lower=True)
+            if rhs.shape[1]:
+                L.solved_W = W
+            VtW = V.T @ W
         return colsumsq, VtW, (V.T @ V if want_cov else None)
 
     # -- fused hot path ------------------------------------------------------------------------------
@@ -289,6 +345,8 @@ class CpuContext:
         info = self.potrf(M)
         if info:
             return np.full((k, k), np.nan), np.nan, info, None
+        if k == 0:                                  # (the fused entry points take k = 0, the operator forward_gram does not)
+            return np.zeros((0, 0)), float(np.log(np.diag(M.A)).sum()), 0, M
         G, sld = self.forward_gram(M, rhs)
         return G, sld, 0, M
 

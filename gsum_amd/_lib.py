@@ -305,6 +305,7 @@ class DeviceMatrix:
         self.n = int(ctx._lib.gsum_mat_n(handle))
         self.factored = False
         self.pivoted = False
+        self.failed = False         # consumed by a failed factorisation (info > 0): only to_host and free take it (include/gsum_hip.h)
         self.piv = None
 
     def to_host(self) -> np.ndarray:
@@ -329,6 +330,19 @@ class DeviceMatrix:
             self.free()
         except Exception:
             pass
+
+
+def _refuse_no_columns(L, n, call):
+    """cho_solve / tri_multiply with zero columns make no device call: the state contract of include/gsum_hip.h is then kept here, from the
+    flags every Python path sets (a ValueError like the library's), so that k = 0 is refused where k = 1 is."""
+    if L.failed:
+        raise ValueError(f"{call}: the matrix was consumed by a failed factorisation (info > 0); upload or build it again")
+    if not L.factored:
+        raise ValueError(f"{call} needs a factorised matrix")
+    if L.pivoted:
+        raise ValueError(f"{call}: the matrix holds a pivoted factor (of P^T A P, in pivot order); only sqrt_errors with pivot = 1 takes it")
+    if n != L.n:
+        raise ValueError(f"{call}: wrong number of rows")
 
 
 class HipContext:
@@ -375,7 +389,8 @@ class HipContext:
 
     def get_option(self, name: str) -> int:
         v = int(self._lib.gsum_get_option(self._h, name.encode()))
-        if v < 0 and name not in ("chain_persist", "chain_probe", "medium_min_batch", "wave_shift", "pipes_ok", "pipe_overlap_permille", "pipe_heals"):
+        if v < 0 and name not in ("chain_persist", "chain_probe", "medium_min_batch", "wave_shift", "pipes_ok", "pipe_overlap_permille", "pipe_heals",
+                                  "chain_fused", "chain_lazy", "chain_deep"):
             raise ValueError(f"unknown option: {name}")
         return v
 
@@ -435,7 +450,7 @@ class HipContext:
         """In-place lower Cholesky; returns LAPACK ``info`` (0 = success)."""
         info = C.c_int64(0)
         self._check(self._lib.gsum_potrf_lower(self._h, A._h, C.byref(info)))
-        A.factored = info.value == 0
+        A.factored, A.failed = info.value == 0, info.value > 0
         return int(info.value)
 
     def factorize(self, desc: KernelDesc, X, diag_add: float = 0.0, series=None):
@@ -461,10 +476,12 @@ class HipContext:
     def pstrf(self, A: DeviceMatrix):
         """LAPACK dpstrf (lower, tol -1) in place: ``(info, piv)`` -- info 0, or rank + 1 where A is rank-deficient (A is then left
         as it was); piv (0-based) with P^T A P = L L^T, and A holds L in pivot order (gsum_sqrt_errors with k = 0)."""
+        if A.factored:              # (the C entry point hands a pivoted factor's pivots out again; a second factorisation is a caller's mistake)
+            raise ValueError("matrix is already factorised")
         info = C.c_int64(0)
         piv = np.empty(A.n, dtype=np.int64)
         self._check(self._lib.gsum_sqrt_errors(self._h, A._h, 1, piv.ctypes.data_as(_ip), C.byref(info), None, None, A.n, 0, None, None))
-        A.factored, A.pivoted, A.piv = info.value == 0, True, piv
+        A.factored, A.failed, A.pivoted, A.piv = info.value == 0, info.value > 0, True, piv
         return int(info.value), piv
 
     def sqrt_errors(self, L: DeviceMatrix, Y, mean=None, pivot: bool = False, errors: bool = True, md2: bool = False):
@@ -486,6 +503,7 @@ class HipContext:
         self._check(self._lib.gsum_sqrt_errors(self._h, L._h, 1 if pivot else 0, piv.ctypes.data_as(_ip) if pivot else None, C.byref(info),
                                                _ptr(Y), _ptr(mean), n, k, _ptr(E), _ptr(m2)))
         if info.value:
+            L.failed = True
             raise np.linalg.LinAlgError(f"{'pstrf' if pivot else 'potrf'}: matrix is not positive definite (info {info.value})")
         L.factored, L.pivoted = True, bool(pivot)
         if pivot:
@@ -523,6 +541,8 @@ class HipContext:
         if squeeze:
             B = B[:, None]
         n, k = B.shape
+        if k == 0:
+            _refuse_no_columns(L, n, "cho_solve")
         out = np.empty((n, k))
         for lo in range(0, k, GSUM_MAX_RHS):
             bc = np.ascontiguousarray(B[:, lo:lo + GSUM_MAX_RHS])
@@ -538,6 +558,8 @@ class HipContext:
         if squeeze:
             Z = Z[:, None]
         n, k = Z.shape
+        if k == 0:
+            _refuse_no_columns(L, n, "tri_multiply")
         out = np.empty((n, k))
         for lo in range(0, k, GSUM_MAX_RHS):
             zc = np.ascontiguousarray(Z[:, lo:lo + GSUM_MAX_RHS])

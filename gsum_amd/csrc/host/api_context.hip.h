@@ -199,6 +199,17 @@ int64_t gsum_get_option(gsum_ctx* ctx, const char* name) {
     if (!strcmp(name, "chain_deep")) return ctx->chain_deep;
     if (!strcmp(name, "chain_depth")) return ctx->chain_depth;
     if (!strcmp(name, "lazy_far")) return ctx->lazy_far;
+    // (what a test moves it reads first and puts back: the lab context is shared by a whole process)
+    if (!strcmp(name, "lazy_min_np")) return ctx->lazy_min_np;
+    if (!strcmp(name, "chain_fused")) return ctx->chain_fused;
+    if (!strcmp(name, "la_depth2")) return ctx->la_depth2;
+    if (!strcmp(name, "chain_lazy")) return ctx->chain_lazy;
+    if (!strcmp(name, "chain_deep_rows")) return ctx->chain_deep_rows;
+    if (!strcmp(name, "predict_lookahead")) return ctx->predict_lookahead;
+    if (!strcmp(name, "predict_depth")) return ctx->predict_depth;
+    if (!strcmp(name, "predict_split")) return ctx->predict_split;
+    if (!strcmp(name, "predict_panel256")) return ctx->predict_panel256;
+    if (!strcmp(name, "predict_lazy")) return ctx->predict_lazy;
     if (!strcmp(name, "panel_wave_ticks") || !strcmp(name, "panel_waves")) {         // read-back of option panel_stats (synchronises)
         if (!ctx->panel_stats) return -1;
         unsigned long long h[2] = {0, 0};

@@ -154,18 +154,21 @@ static int gs_potrf_info(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
         ctx->chain_persist = 0;
         ++ctx->chain_aborts;
         A->factored = false;
+        A->failed = true;
         ctx->err = "the persistent chain schedule timed out (streams of this process do not run side by side); the matrix is "
                    "destroyed -- rebuild it and factorise again: the schedule is now switched off (option chain_persist = 0)";
         return GSUM_ERR_CHAIN_ABORT;        // a runtime failure the caller can recover from: rebuild the matrix, factorise again
     }
     if (*info > A->n) *info = A->n;     // cannot happen (identity padding), kept as a guard
     A->factored = (*info == 0);
+    A->failed = (*info > 0);            // partly overwritten: no input any more, and no factor
     return 0;
 }
 
 int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info) {
     if (!ctx || !A || !info) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
+    if (gs_refuse_failed(ctx, A, "potrf")) return -2;
     if (A->factored) GS_FAIL("matrix is already factorised");
     A->pivoted = 0;
     return gs_potrf_info(ctx, A, info);
@@ -205,7 +208,7 @@ int gsum_forward_gram(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, 
                       double* sum_log_diag) {
     if (!ctx || !L || !G || !sum_log_diag) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
-    if (!L->factored) GS_FAIL("forward_gram needs a factorised matrix");
+    if (gs_need_factor(ctx, L, "forward_gram")) return -2;
     if (n != L->n) GS_FAIL("RHS has the wrong number of rows");
     if (k < 1 || k > GSUM_MAX_RHS) GS_FAIL("k must be 1..GSUM_MAX_RHS");
     GS_CHECK(hipMemsetAsync(ctx->cur->dinfo, 0, sizeof(int), ctx->cur->sm));
@@ -221,7 +224,7 @@ int gsum_forward_gram(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, 
 int gsum_forward_solve(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, int32_t k, double* W) {
     if (!ctx || !L || !W) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
-    if (!L->factored) GS_FAIL("forward_solve needs a factorised matrix");
+    if (gs_need_factor(ctx, L, "forward_solve")) return -2;
     if (n != L->n) GS_FAIL("RHS has the wrong number of rows");
     if (k < 1 || k > GSUM_MAX_RHS) GS_FAIL("k must be 1..GSUM_MAX_RHS");
     if (gs_border_prepare(ctx, L, RHS, n, k)) return -1;
@@ -240,7 +243,7 @@ int gsum_forward_solve(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n,
 int gsum_cho_solve(gsum_ctx* ctx, gsum_mat* L, const double* B, int64_t n, int32_t k, double* X) {
     if (!ctx || !L || !B || !X) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
-    if (!L->factored) GS_FAIL("cho_solve needs a factorised matrix");
+    if (gs_need_factor(ctx, L, "cho_solve")) return -2;
     if (n != L->n) GS_FAIL("B has the wrong number of rows");
     if (k < 1 || k > GSUM_MAX_RHS) GS_FAIL("k must be 1..GSUM_MAX_RHS");
     hipStream_t s = ctx->cur->sm;
@@ -267,7 +270,7 @@ int gsum_cho_solve(gsum_ctx* ctx, gsum_mat* L, const double* B, int64_t n, int32
 int gsum_tri_multiply(gsum_ctx* ctx, gsum_mat* L, const double* Z, int64_t n, int32_t k, double* out) {
     if (!ctx || !L || !Z || !out) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
-    if (!L->factored) GS_FAIL("tri_multiply needs a factorised matrix");
+    if (gs_need_factor(ctx, L, "tri_multiply")) return -2;
     if (n != L->n) GS_FAIL("Z has the wrong number of rows");
     if (k < 1 || k > GSUM_MAX_RHS) GS_FAIL("k must be 1..GSUM_MAX_RHS");
     if (gs_reserve(ctx, &ctx->scratch, &ctx->scratch_cap, (size_t)2 * n * 16 * 8)) return -1;
@@ -298,6 +301,7 @@ static int gs_check_series(gsum_ctx* ctx, const gsum_series_scale* sc) {
 int gsum_mat_scale_series(gsum_ctx* ctx, gsum_mat* A, const gsum_series_scale* sc, const double* ref, const double* ratio) {
     if (!ctx || !A || !sc || !ref || !ratio) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
+    if (gs_refuse_failed(ctx, A, "scale_series")) return -2;
     if (A->factored) GS_FAIL("scale_series needs an unfactored matrix");
     if (gs_check_series(ctx, sc)) return -2;
     const int64_t n = A->n;
@@ -332,6 +336,7 @@ int gsum_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc,
 int gsum_predict_var(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n, int32_t d, const double* Xs,
                      int64_t m, double* colsumsq, double* VtW) {
     if (!ctx || !L) return -2;
+    if (gs_need_factor(ctx, L, "predict_var")) return -2;
     if (VtW && L->solved_k <= 0) GS_FAIL("gsum_predict_var: V^T W needs right-hand sides solved against this factor first (gsum_forward_gram)");
     const int k = VtW ? L->solved_k : 0;
     const std::vector<double> rhs = VtW ? L->solved_rhs : std::vector<double>();       // (a copy: gs_border_prepare compares against the original)
@@ -484,7 +489,7 @@ static int gs_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* 
     if (!ctx || !L || !X || !Xs || !colsumsq) return -2;
     GS_CHECK(hipSetDevice(ctx->device));
     if (gs_check_desc(ctx, desc, d)) return -2;
-    if (!L->factored) GS_FAIL("predict_terms needs a factorised matrix");
+    if (gs_need_factor(ctx, L, "predict_terms")) return -2;
     if (n != L->n || m <= 0) GS_FAIL("bad shapes");
     if (k < 0 || k > GSUM_MAX_RHS || (k > 0 && (!RHS || !VtW))) GS_FAIL("bad RHS / k");
     const int64_t np = L->np, ld = L->ld, ldb = np + GS_BORDER;

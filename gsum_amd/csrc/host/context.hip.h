@@ -32,6 +32,8 @@ struct gsum_mat {
     double* cdump = nullptr;               // 2 x GS_CH_GMAX x 16 x 256 doubles: operand images of the window's rows
     unsigned long long* cstamps = nullptr; // T / 2 x GS_CH_STAMPS realtime stamps (option "chain_stamps")
     bool factored = false;
+    bool failed = false;                   // consumed by a failed factorisation (potrf / pstrf reported info > 0, or the chain schedule gave up):
+                                           // what the matrix holds is no input and no factor -- only gsum_mat_to_host and gsum_mat_free take it
     int pivoted = 0;                       // the factor is of P^T A P (gsum_sqrt_errors, pivot = 1): A's rows / columns in pivot order
     int* dperm = nullptr;                  // ... and P on the device (n entries: original index of row i), and on the host
     std::vector<int64_t> perm;
@@ -288,6 +290,20 @@ enum { GS_PROF_BUILD = 0, GS_PROF_DIAG = 1, GS_PROF_PANEL = 2, GS_PROF_BULK = 3,
         ctx->err = (msg);       \
         return -2;              \
     } while (0)
+
+// The state contract of the operator level (include/gsum_hip.h): what a call named `call` may be handed.
+//   gs_refuse_failed: anything but a matrix consumed by a failed factorisation (every call but to_host and free asks this first)
+//   gs_need_factor: an unpivoted Cholesky factor (forward_gram, forward_solve, cho_solve, tri_multiply, predict_terms / predict_var)
+static int gs_refuse_failed(gsum_ctx* ctx, const gsum_mat* m, const char* call) {
+    if (m->failed) GS_FAIL(std::string(call) + ": the matrix was consumed by a failed factorisation (info > 0); upload or build it again");
+    return 0;
+}
+static int gs_need_factor(gsum_ctx* ctx, const gsum_mat* m, const char* call) {
+    if (gs_refuse_failed(ctx, m, call)) return -2;
+    if (!m->factored) GS_FAIL(std::string(call) + " needs a factorised matrix");
+    if (m->pivoted) GS_FAIL(std::string(call) + ": the matrix holds a pivoted factor (of P^T A P, in pivot order); only sqrt_errors with pivot = 1 takes it");
+    return 0;
+}
 
 static int gs_reserve(gsum_ctx* ctx, double** p, size_t* cap, size_t bytes) {
     if (*cap >= bytes && *p) return 0;

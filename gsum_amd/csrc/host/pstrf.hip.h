@@ -128,6 +128,7 @@ int gsum_sqrt_errors(gsum_ctx* ctx, gsum_mat* A, int32_t pivot, int64_t* piv, in
     if (n != A->n) GS_FAIL("sqrt_errors: n differs from the matrix order");
     if (k < 0) GS_FAIL("sqrt_errors: k must be >= 0");
     if (k > 0 && (E || md2) && !Y) GS_FAIL("sqrt_errors: Y is NULL");
+    if (gs_refuse_failed(ctx, A, "sqrt_errors")) return -2;
     *info = 0;
     if (!A->factored) {
         A->solved_k = -1;
@@ -136,7 +137,10 @@ int gsum_sqrt_errors(gsum_ctx* ctx, gsum_mat* A, int32_t pivot, int64_t* piv, in
         if (rc) return rc;
         if (pivot && piv)
             for (int64_t i = 0; i < n; ++i) piv[i] = A->perm[(size_t)i];
-        if (*info > 0) return 0;
+        if (*info > 0) {
+            A->failed = true;           // (a rank-deficient search leaves A's entries as they were, a failed potrf does not: refused alike)
+            return 0;
+        }
     } else {
         if (A->pivoted != pivot)
             GS_FAIL(A->pivoted ? "sqrt_errors: the matrix holds a pivoted factor (pivot = 1)" : "sqrt_errors: the matrix holds an unpivoted factor (pivot = 0)");

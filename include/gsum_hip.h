@@ -126,32 +126,44 @@ int gsum_kernel_build_series(gsum_ctx* ctx, const gsum_kernel_desc* desc, const 
  * Orders: 1 .. 46000 (validated to 40960; a padded matrix of 2^31 elements or more is refused with an error, never attempted). */
 int gsum_kernel_build_dev(gsum_ctx* ctx, const gsum_kernel_desc* desc, const double* X, int64_t n, int32_t d,
                           double diag_add, gsum_mat** out);
-/* upload a caller-built symmetric matrix (only its lower triangle is read) */
+/* A matrix handle is an INPUT (built or uploaded), a FACTOR (a factorisation reported *info == 0), a PIVOTED factor (of P^T A P, rows in
+ * pivot order: gsum_sqrt_errors with pivot = 1) or FAILED (a factorisation reported *info > 0, or GSUM_ERR_CHAIN_ABORT).  "Refuses" below:
+ * returns -2 with a message that names the call, and changes nothing.
+ * upload a caller-built symmetric matrix (only its lower triangle is read) */
 int gsum_mat_from_host(gsum_ctx* ctx, const double* A, int64_t n, gsum_mat** out);
 /* numpy.linalg.cholesky(A), in place on the device.  Replaces models.py:711, 809, 969.  *info = LAPACK dpotrf's info.
  * GSUM_ERR_CHAIN_ABORT: the persistent-chain schedule of a single factorisation timed out (streams of the process did not run
- * side by side); the matrix is destroyed and the schedule switched off for the context -- rebuild the matrix and call again. */
+ * side by side); the matrix is destroyed and the schedule switched off for the context -- rebuild the matrix and call again.
+ * Refuses a FACTOR, a PIVOTED factor, a FAILED matrix.  *info > 0 leaves the matrix FAILED (it is partly overwritten): only
+ * gsum_mat_to_host and gsum_mat_free take it from then on. */
 #define GSUM_ERR_CHAIN_ABORT (-3)
 int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info);
 /* W = L^-1 RHS (forward substitution only), G = W^T W (k x k), sum_log_diag = sum_i log L_ii.  Replaces the cho_solve calls
- * at models.py:432, 438, 439, 1032 (+269, 217), the reductions at :433, 1015, 1035 and the N x N temporary at :441-442. */
+ * at models.py:432, 438, 439, 1032 (+269, 217), the reductions at :433, 1015, 1035 and the N x N temporary at :441-442.
+ * Refuses an INPUT, a PIVOTED factor, a FAILED matrix, n != the order, k outside 1 .. GSUM_MAX_RHS.  The factor then HOLDS the solve. */
 int gsum_forward_gram(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, int32_t k, double* G, double* sum_log_diag);
-/* W = L^-1 RHS (n x k host): the forward half of cho_solve (models.py:479; with gsum_predict_terms: the solve at :831) */
+/* W = L^-1 RHS (n x k host): the forward half of cho_solve (models.py:479; with gsum_predict_terms: the solve at :831)
+ * Refusals and the held solve as gsum_forward_gram. */
 int gsum_forward_solve(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, int32_t k, double* W);
-/* X = cho_solve((L, True), B): both triangular solves of solve_sqrt (models.py:460-479); B, X n x k host, k <= GSUM_MAX_RHS */
+/* X = cho_solve((L, True), B): both triangular solves of solve_sqrt (models.py:460-479); B, X n x k host, k <= GSUM_MAX_RHS
+ * Refusals as gsum_forward_gram.  The factor holds NO solve afterwards (the back-substitution runs in place on the border rows). */
 int gsum_cho_solve(gsum_ctx* ctx, gsum_mat* L, const double* B, int64_t n, int32_t k, double* X);
-/* out = L Z (n x k): draws from N(mean, L L^T) without the n x n SVD of models.py:869-876, datasets.py:69-70 */
+/* out = L Z (n x k): draws from N(mean, L L^T) without the n x n SVD of models.py:869-876, datasets.py:69-70
+ * Refusals as gsum_forward_gram; a held solve stays. */
 int gsum_tri_multiply(gsum_ctx* ctx, gsum_mat* L, const double* Z, int64_t n, int32_t k, double* out);
 /* Predictive pieces for m new points Xs (models.py:822-836) from the factor of kernel(X) + nugget: V = L^-1 kernel(X, Xs);
- * colsumsq[j] = sum_i V_ij^2;  VtW = V^T (L^-1 RHS) (m x k; NULL / k = 0 to skip);  cov_out (or NULL) = V^T V (m x m). */
+ * colsumsq[j] = sum_i V_ij^2;  VtW = V^T (L^-1 RHS) (m x k; NULL / k = 0 to skip);  cov_out (or NULL) = V^T V (m x m).
+ * Refuses an INPUT, a PIVOTED factor, a FAILED matrix, n != the order, m <= 0, k outside 0 .. GSUM_MAX_RHS.  k > 0: HOLDS the solve. */
 int gsum_predict_terms(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n, int32_t d,
                        const double* Xs, int64_t m, const double* RHS, int32_t k, double* colsumsq, double* VtW, double* cov_out);
 /* the same under SURVEY.md section 8b's name: colsumsq (m) and, optionally, VtW (m x GSUM_MAX_RHS, columns >= k zero) for the k right-hand
  * sides whose forward solve the factor already holds (the last gsum_forward_gram / gsum_forward_solve on it): predict after fit without
- * handing the residuals over again (models.py:822-836) */
+ * handing the residuals over again (models.py:822-836)
+ * Refusals as gsum_predict_terms; with VtW also a factor that holds no solve (a fresh one, or one after gsum_cho_solve). */
 int gsum_predict_var(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n, int32_t d,
                      const double* Xs, int64_t m, double* colsumsq, double* VtW);
-/* in-place series scaling of an unfactored device matrix (ref, ratio: n host values): K_oo of models.py:1443, 1466 */
+/* in-place series scaling of an unfactored device matrix (ref, ratio: n host values): K_oo of models.py:1443, 1466
+ * Refuses a FACTOR, a PIVOTED factor, a FAILED matrix. */
 int gsum_mat_scale_series(gsum_ctx* ctx, gsum_mat* A, const gsum_series_scale* sc, const double* ref, const double* ratio);
 /* gsum_predict_terms with kernel(X, Xs) scaled like cov(X, Xs, start, end) first: the pieces of models.py:1449-1452, 1470-1473 */
 int gsum_predict_terms_series(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc* desc, const double* X, int64_t n, int32_t d,
@@ -160,10 +172,14 @@ int gsum_predict_terms_series(gsum_ctx* ctx, gsum_mat* L, const gsum_kernel_desc
                               double* colsumsq, double* VtW, double* cov_out);
 /* Diagnostic square roots (gsum diagnostics.py:58-61, 100-114; helpers.py:185-199): an unfactored A is factorised in place first -- pivot 0
  * as gsum_potrf_lower, 1 as LAPACK dpstrf (lower, tol -1; piv: n 0-based); *info 0, or (rank | bad pivot) + 1.  Then, any k >= 0:
- * E = L^-1 P^T (Y - mean 1^T) (n x k row-major; NULL: skip), md2[j] = sum_i E_ij^2 (NULL: skip).  Full contract: DESIGN.md section 11. */
+ * E = L^-1 P^T (Y - mean 1^T) (n x k row-major; NULL: skip), md2[j] = sum_i E_ij^2 (NULL: skip).  Full contract: DESIGN.md section 11.
+ * Refuses a FAILED matrix, a factor of the other kind (pivot = 1 on a FACTOR, pivot = 0 on a PIVOTED one), n != the order, k < 0.
+ * *info > 0 leaves the matrix FAILED (after a rank-deficient pivot search its entries are still A's; gsum_mat_to_host returns them).
+ * On a PIVOTED factor, pivot = 1 with k = 0 hands the pivots out again (gsum_amd's pstrf wrapper refuses a second factorisation). */
 int gsum_sqrt_errors(gsum_ctx* ctx, gsum_mat* A, int32_t pivot, int64_t* piv, int64_t* info, const double* Y, const double* mean,
                      int64_t n, int64_t k, double* E, double* md2);
-/* copy out: the full symmetric matrix (before potrf) or L with a zeroed upper triangle (after) */
+/* copy out: the full symmetric matrix (before potrf) or L with a zeroed upper triangle (after); every state is taken (FAILED: what
+ * the failed potrf left behind, or A itself after a rank-deficient pivot search) */
 int gsum_mat_to_host(gsum_ctx* ctx, const gsum_mat* A, double* out);
 int64_t gsum_mat_n(const gsum_mat* A);
 void gsum_mat_free(gsum_ctx* ctx, gsum_mat* A);

@@ -20,7 +20,9 @@ extern "C" {
  *   enqueued between the factorisation's outer steps), "grad_split" (Q_p beside the R^-1 product, traces from stored dR triangles), "grad_lazy_chain"
  * single factorisation: "chain_rows" 256 | 512, "chain_lazy", "chain_min_np", "chain_fused", "chain_prefetch", "la_depth2",
  *   "bulk_lds_pad", "chain_test_abort" (one-shot give-up of the persistent chain at that outer step), "chain_stamps"
- * other sweeps: "predict_lazy", "medium_lazy", "build_lower_only", "diag_stamps", "panel_stats", "bench_fill" */
+ * other sweeps: "predict_lazy", "medium_lazy", "build_lower_only", "diag_stamps", "panel_stats", "bench_fill"
+ * gsum_get_option reads back what a test moves and must put back: "lazy_far", "lazy_min_np", "wave_deep_rows", "chain_rows", "chain_lazy",
+ *   "chain_fused", "la_depth2", "chain_deep", "chain_depth", "chain_deep_rows", "predict_lookahead" / "_depth" / "_split" / "_panel256" / "_lazy" */
 
 /* diagnostic: the 64 raw stamp words of the last diagonal-block kernel run with "diag_stamps" = 1 ([0..4] as above;
  * round-2 kernel: [7] start, [8 + 2j], [9 + 2j] wave 0 behind the two barriers of micro-block column j, [24 + j] cycles
