@@ -33,12 +33,20 @@ PROTOTYPES = {
     "gsum_toep_gram_panel": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_predict_panel": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_panel_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_toep_blocked_max_n": (C.c_int64, [_p]),
+    "gsum_toep_blocked_tile_rows": (C.c_int32, [_p]),
+    "gsum_toep_gram_blocked": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_predict_blocked": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_blocked_times": (C.c_int, [_p, _dp, C.c_int32]),
 }
 PHASES = ("h2d", "schur", "gram", "d2h")
 GRAD_PHASES = ("h2d", "schur", "levinson", "gram", "diagsums", "solve", "contract", "d2h")    # of grad and solve (gsum_toep_grad_times)
 POST_PHASES = ("h2d", "schur", "levinson", "sums", "cov", "solve", "d2h")                     # of predict and loo (gsum_toep_post_times)
 PANEL_PHASES = ("h2d", "recursion", "diag", "update", "sums", "cov", "d2h")                     # of the panel route (gsum_toep_panel_times)
-METHODS = ("columns", "panel")                                         # the device schedules of gram and predict
+BLOCKED_PHASES = ("h2d", "lead", "tiles", "diag", "update", "sums", "cov", "d2h")               # of the blocked route (gsum_toep_blocked_times)
+METHODS = ("columns", "panel", "blocked")                              # the device schedules of gram and predict
+_GRAM = {"columns": "gsum_toep_gram", "panel": "gsum_toep_gram_panel", "blocked": "gsum_toep_gram_blocked"}
+_PREDICT = {"columns": "gsum_toep_predict", "panel": "gsum_toep_predict_panel", "blocked": "gsum_toep_predict_blocked"}
 MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
 
 
@@ -51,9 +59,10 @@ def _check(lib, rc):
     _sidelib.check(lib, rc, "gsum_toep_last_error")
 
 
-def max_n():
-    """The largest n ``DeviceToeplitz.gram`` takes (needs no device)."""
-    return int(load_library().gsum_toep_max_n(None))
+def max_n(method="columns"):
+    """The largest n ``DeviceToeplitz.gram`` takes with ``method`` (needs no device)."""
+    lib = load_library()
+    return int(lib.gsum_toep_blocked_max_n(None) if check_method(method) == "blocked" else lib.gsum_toep_max_n(None))
 
 
 def panel_width():
@@ -61,11 +70,16 @@ def panel_width():
     return int(load_library().gsum_toep_panel_width(None))
 
 
+def blocked_tile_rows():
+    """The rows a tile of the blocked route owns (needs no device)."""
+    return int(load_library().gsum_toep_blocked_tile_rows(None))
+
+
 def check_method(method, name="method"):
     """The one check of ``method=`` / ``toeplitz_method=`` (``name``).  The keyword selects a device schedule, not an arithmetic:
-    ``backend='cpu'`` accepts both values and runs its one code."""
-    if method not in METHODS:
-        raise ValueError(f'{name} must be "columns" or "panel", got {method!r}')
+    ``backend='cpu'`` accepts every value and runs its one code."""
+    if not isinstance(method, str) or method not in METHODS:
+        raise ValueError(f'{name} must be "columns" or "panel" or "blocked", got {method!r}')
     return method
 
 
@@ -89,8 +103,8 @@ class DeviceToeplitz(DeviceHandle):
 
     def gram(self, t, Z, n_sets, method="columns"):
         """(G (m, n_sets, c, c), sum_log_diag (m,), info (m,) int32) of the first columns t (m, n) and the right-hand sides Z
-        (n, n_sets * c): gsum_toep_gram, or gsum_toep_gram_panel with ``method="panel"``."""
-        fn = self._lib.gsum_toep_gram_panel if check_method(method) == "panel" else self._lib.gsum_toep_gram
+        (n, n_sets * c): gsum_toep_gram, gsum_toep_gram_panel with ``method="panel"`` or gsum_toep_gram_blocked with ``"blocked"``."""
+        fn = getattr(self._lib, _GRAM[check_method(method)])
         t = np.ascontiguousarray(t, dtype=np.float64)
         Zf = np.asfortranarray(Z, dtype=np.float64)
         m, n = t.shape
@@ -141,9 +155,9 @@ class DeviceToeplitz(DeviceHandle):
 
     def predict(self, t, K, Z, want_cov, method="columns"):
         """(quad (q,), cross (q, c), cov (q, q) or None, G (c, c), sum_log_diag, info) of one first column t (n,), the cross-covariance
-        columns K (n, q) and the residual columns Z (n, c), c >= 0: gsum_toep_predict, or gsum_toep_predict_panel with
-        ``method="panel"``."""
-        fn = self._lib.gsum_toep_predict_panel if check_method(method) == "panel" else self._lib.gsum_toep_predict
+        columns K (n, q) and the residual columns Z (n, c), c >= 0: gsum_toep_predict, gsum_toep_predict_panel with
+        ``method="panel"`` or gsum_toep_predict_blocked with ``"blocked"``."""
+        fn = getattr(self._lib, _PREDICT[check_method(method)])
         t = np.ascontiguousarray(t, dtype=np.float64)
         Kf = np.asfortranarray(K, dtype=np.float64)
         Zf = np.asfortranarray(Z, dtype=np.float64)
@@ -173,6 +187,10 @@ class DeviceToeplitz(DeviceHandle):
             _check(self._lib, self._lib.gsum_toep_loo(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, _d(p),
                                                       None if alpha is None else _d(alpha), _i32(info)))
         return p, alpha, info
+
+    def blocked_times(self, reset=False):
+        """Device milliseconds spent so far by ``gram`` and ``predict`` with ``method="blocked"``, by phase (BLOCKED_PHASES)."""
+        return self._phase_times("gsum_toep_blocked_times", BLOCKED_PHASES, reset)
 
     def panel_times(self, reset=False):
         """Device milliseconds spent so far by ``gram`` and ``predict`` with ``method="panel"``, by phase (PANEL_PHASES)."""

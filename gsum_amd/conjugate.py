@@ -833,7 +833,9 @@ class ConjugateGaussianProcess:
         ``structure_`` is ``"toeplitz"`` and ``corr_L_`` None, and ``predict``, ``loo`` and ``sample_y`` follow the structured route
         (DESIGN.md section 20).  ``kfold``, ``predict(devices=...)`` and the 'eig' attributes need the dense factor and say so.
         ``toeplitz_method`` (``toeplitz_predict``'s ``method=``): a fit with ``dense_factor=False`` remembers it for ``predict`` and
-        ``sample_y``; the calibration, with at most one set of columns, stays on the column route."""
+        ``sample_y``; the calibration, with at most one set of columns, stays on the column route.  With ``"blocked"`` (DESIGN.md
+        section 23) the final ``toeplitz_gram`` takes that route too, so ``optimizer=None`` with ``dense_factor=False`` fits and
+        predicts beyond ``toeplitz_max_n()``; the gradient of a calibration keeps that limit and says so."""
         self._check_decomposition()
         from ._toep_lib import check_method
         self._toeplitz_method = check_method(toeplitz_method, "toeplitz_method")
@@ -889,7 +891,9 @@ class ConjugateGaussianProcess:
             self._L_dev, info = ctx.factorize(desc, Xd, diag_add=self.nugget)
         else:                                     # the structured route to the end: G and sum_log_diag of the fitted kernel's first column
             from .toeplitz import column_of_desc, toeplitz_gram
-            G, sld, info = toeplitz_gram(column_of_desc(ctx, desc, Xd, self.nugget), Z, 1, device=self.device, backend=self.backend)
+            # the blocked route alone reaches beyond toeplitz_max_n(): a fit asked for it takes it here too, every other fit the column route
+            method = "blocked" if self._toeplitz_method == "blocked" else "columns"
+            G, sld, info = toeplitz_gram(column_of_desc(ctx, desc, Xd, self.nugget), Z, 1, device=self.device, backend=self.backend, method=method)
         if info != 0:
             if self._L_dev is not None:
                 self._L_dev.free()

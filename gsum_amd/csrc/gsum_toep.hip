@@ -21,6 +21,12 @@ enum GradPhase { kGH2D = kPhases, kGSchur, kGLevinson, kGGram, kGDiag, kGSolve, 
 enum PostPhase { kPH2D = kAllPhases, kPSchur, kPLevinson, kPSums, kPCov, kPSolve, kPD2H, kEveryPhase };
 // the phases of gsum_toep_gram_panel and gsum_toep_predict_panel (gsum_toep_panel_times), after those
 enum PanelPhase { kNH2D = kEveryPhase, kNRecursion, kNDiag, kNUpdate, kNSums, kNCov, kND2H, kTotalPhases };
+// the phases of gsum_toep_gram_blocked and gsum_toep_predict_blocked (gsum_toep_blocked_times), after those
+enum BlockedPhase { kBH2D = kTotalPhases, kBLead, kBTiles, kBDiag, kBUpdate, kBSums, kBCov, kBD2H, kGrandPhases };
+
+static_assert((GSUM_TOEP_BLOCKED_MAX_N - gt::kPanelB + 15) / 16 <= 65535 && (GSUM_TOEP_BLOCKED_MAX_N + 31) / 32 <= 65535,
+              "k_panel_update's and k_panel_load's grid y at the blocked route's limit");
+constexpr int kBlockedSettle = 256;                // panels of the blocked route between two settlements of the phase clock's events
 
 constexpr size_t kYBudget = (size_t)256 << 20;     // bytes of solved columns (Y) in flight: the first columns go through in chunks
 // the panel route's: the solved columns with their correction words, the panel and the generator state of the first columns in flight
@@ -28,13 +34,14 @@ constexpr size_t kPanelBudget = (size_t)1 << 30;
 
 }  // namespace
 
-struct gsum_toep : TimedHandle<kTotalPhases> {
+struct gsum_toep : TimedHandle<kGrandPhases> {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
     DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
     DevBuf<double, true> Yz, quad, cross, cov, pd;                             // the posterior's
     DevBuf<double, true> Ph, Pst;                                              // the panel route's: a panel's high words, the generator state
     DevBuf<float, true> Pl, Zc;                                                // ... its low words, the correction words beside Y
+    DevBuf<double, true> Bst, Bco, Bdg;                                        // the blocked route's: two generator states, a panel's coefficients, diag(L)
 };
 
 namespace {
@@ -108,9 +115,8 @@ int64_t columns_per_launch(int64_t m, size_t bytes, size_t budget = kYBudget) {
 }
 
 // What the entry point `who` refuses about the first columns: their order n ...
-void check_order(const char* who, int64_t n) {
-    if (n > gt::kMaxN)
-        throw Error(std::string(who) + ": n must be <= " + std::to_string(gt::kMaxN) + " (one workgroup holds the generator), got " + std::to_string(n));
+void check_order(const char* who, int64_t n, int64_t limit = gt::kMaxN, const char* why = "one workgroup holds the generator") {
+    if (n > limit) throw Error(std::string(who) + ": n must be <= " + std::to_string(limit) + " (" + why + "), got " + std::to_string(n));
 }
 
 // ... and their scale (`with`: what else the hint says to scale).  The right-hand sides are normalised on the device (k_colexp); the
@@ -248,15 +254,39 @@ void reserve_panel(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
     h->Pst.reserve(4 * ne * step);
 }
 
-// Y = L^-1 Z of cnt first columns t (device) and the ncols columns h->Z / h->ze, with sum_log_diag and info: per panel of kPanelB
-// columns of L the recursion, the triangular block and the trailing update, one after the other on the handle's stream.
-void panel_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+// The scaled right-hand sides h->Z / h->ze into the working residuals h->Y of cnt first columns, their correction words zeroed.
+void load_residuals(gsum_toep* h, int n, int ncols, int64_t cnt, int phase) {
     hipStream_t st = h->stream;
-    timed(h, kNUpdate, [&] {
+    timed(h, phase, [&] {
         gt::k_panel_load<<<dim3((unsigned)((ncols + 31) / 32), (unsigned)((n + 31) / 32)), dim3(32, 8), 0, st>>>(h->Z.p, h->ze.p, n, ncols, (int)cnt, h->Y.p);
         SL_LAUNCHED("k_panel_load");
         SL_CHECK(hipMemsetAsync(h->Zc.p, 0, sizeof(float) * (size_t)n * ncols * cnt, st));
     });
+}
+
+// The panel h->Ph / h->Pl of the columns k0 .. of L against every right-hand side: its triangular block, then the rows below it.
+void apply_panel(gsum_toep* h, int n, int k0, int ncols, int64_t cnt, const int32_t* info, int phase_diag, int phase_update) {
+    hipStream_t st = h->stream;
+    timed(h, phase_diag, [&] {
+        const dim3 grid((unsigned)((ncols + gt::kDiagThreads - 1) / gt::kDiagThreads), (unsigned)cnt);
+        gt::k_panel_diag<<<grid, gt::kDiagThreads, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
+        SL_LAUNCHED("k_panel_diag");
+    });
+    const int below = n - k0 - gt::kPanelB;                                    // rows under the panel
+    if (below > 0)
+        timed(h, phase_update, [&] {
+            const int wide = 16 * gt::kUpdateTiles;
+            const dim3 grid((unsigned)((ncols + wide - 1) / wide), (unsigned)((below + 15) / 16), (unsigned)cnt);
+            gt::k_panel_update<<<grid, gt::kWave, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
+            SL_LAUNCHED("k_panel_update");
+        });
+}
+
+// Y = L^-1 Z of cnt first columns t (device) and the ncols columns h->Z / h->ze, with sum_log_diag and info: per panel of kPanelB
+// columns of L the recursion, the triangular block and the trailing update, one after the other on the handle's stream.
+void panel_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+    hipStream_t st = h->stream;
+    load_residuals(h, n, ncols, cnt, kNUpdate);
     for (int k0 = 0; k0 < n; k0 += gt::kPanelB) {
         timed(h, kNRecursion, [&] {
             with_size_class(n, [&](auto k) {
@@ -265,20 +295,185 @@ void panel_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, d
             });
             SL_LAUNCHED("k_schur_panel");
         });
-        timed(h, kNDiag, [&] {
-            const dim3 grid((unsigned)((ncols + gt::kDiagThreads - 1) / gt::kDiagThreads), (unsigned)cnt);
-            gt::k_panel_diag<<<grid, gt::kDiagThreads, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
-            SL_LAUNCHED("k_panel_diag");
-        });
-        const int below = n - k0 - gt::kPanelB;                                // rows under the panel
-        if (below > 0)
-            timed(h, kNUpdate, [&] {
-                const int wide = 16 * gt::kUpdateTiles;
-                const dim3 grid((unsigned)((ncols + wide - 1) / wide), (unsigned)((below + 15) / 16), (unsigned)cnt);
-                gt::k_panel_update<<<grid, gt::kWave, 0, st>>>(h->Ph.p, h->Pl.p, n, k0, ncols, h->Y.p, h->Zc.p, info);
-                SL_LAUNCHED("k_panel_update");
-            });
+        apply_panel(h, n, k0, ncols, cnt, info, kNDiag, kNUpdate);
     }
+}
+
+// ---- the blocked route ----
+
+// Bytes one first column keeps on the device on the blocked route: Y with its correction words, one panel, the two generator
+// states, the panel's coefficients and the diagonal of L.
+size_t blocked_bytes(int64_t n, int64_t ncols) {
+    return (size_t)n * ncols * (sizeof(double) + sizeof(float)) + (size_t)n * gt::kPanelB * (sizeof(double) + sizeof(float)) +
+           ((size_t)2 * 4 * n + 4 * gt::kPanelB + n) * sizeof(double);
+}
+
+// The buffers of `step` first columns in flight on the blocked route.
+void reserve_blocked(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
+    h->Y.reserve((size_t)n * ncols * step);
+    h->Zc.reserve((size_t)n * ncols * step);
+    h->Ph.reserve((size_t)n * gt::kPanelB * step);
+    h->Pl.reserve((size_t)n * gt::kPanelB * step);
+    h->Bst.reserve((size_t)2 * 4 * n * step);
+    h->Bco.reserve((size_t)4 * gt::kPanelB * step);
+    h->Bdg.reserve((size_t)n * step);
+}
+
+// panel_solve with the recursion of a panel split into its lead and its tiles: per panel k_schur_lead, k_schur_tiles (from one state
+// buffer into the other), then the panel route's triangular block and trailing update on the panel the tiles stored.
+void blocked_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+    hipStream_t st = h->stream;
+    load_residuals(h, n, ncols, cnt, kBUpdate);
+    double* cur = h->Bst.p;
+    double* nxt = cur + (size_t)4 * n * cnt;
+    timed(h, kBTiles, [&] {
+        gt::k_blocked_init<<<dim3((unsigned)((n + 255) / 256), (unsigned)cnt), 256, 0, st>>>(t, n, cur, info);
+        SL_LAUNCHED("k_blocked_init");
+    });
+    int panels = 0;
+    for (int k0 = 0; k0 < n; k0 += gt::kPanelB) {
+        timed(h, kBLead, [&] {
+            gt::k_schur_lead<<<(unsigned)cnt, gt::kWave, 0, st>>>(n, k0, cur, h->Bco.p, info);
+            SL_LAUNCHED("k_schur_lead");
+        });
+        timed(h, kBTiles, [&] {
+            const dim3 grid((unsigned)((n - 1) / gt::kTileR - k0 / gt::kTileR + 1), (unsigned)cnt);      // the tiles from the pivot's on
+            gt::k_schur_tiles<<<grid, gt::kWave, 0, st>>>(n, k0, cur, nxt, h->Bco.p, h->Ph.p, h->Pl.p, h->Bdg.p, info);
+            SL_LAUNCHED("k_schur_tiles");
+        });
+        // both buffers are required: a tile's halo is its upper neighbour's own rows, and nothing orders the tiles of one launch, so a
+        // tile may load after its neighbour has stored.  No test sees a single buffer fail (the hardware starts neighbours together).
+        std::swap(cur, nxt);
+        apply_panel(h, n, k0, ncols, cnt, info, kBDiag, kBUpdate);
+        // a large n has thousands of panels with four event pairs each: settle them every kBlockedSettle panels, which costs one
+        // stream synchronisation each time (64 of them at n = 2^20, none before the last panel at n <= 16384)
+        if (++panels % kBlockedSettle == 0) settle(h);
+    }
+    timed(h, kBTiles, [&] {
+        int E = (n + gt::kThreads - 1) / gt::kThreads;                         // beyond the size classes; within them k_schur's own
+        if (n <= gt::kMaxN) with_size_class(n, [&](auto k) { E = decltype(k)::E; });
+        gt::k_blocked_sld<<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->Bdg.p, n, E, sld, info);
+        SL_LAUNCHED("k_blocked_sld");
+    });
+}
+
+// What the panel and the blocked entry points differ in: the limit on n, the phases they charge, the device memory of a first
+// column, and the solve.  Everything around the solve is one code (gram_route, predict_route).
+struct Route {
+    int64_t max_n;
+    const char* why;                                                           // what bounds n, for the refusal
+    int h2d, prepare, sums, cov, d2h;
+    size_t (*bytes)(int64_t, int64_t);
+    void (*reserve)(gsum_toep*, int64_t, int64_t, int64_t);
+    void (*solve)(gsum_toep*, const double*, int, int, int64_t, double*, int32_t*);
+};
+const Route kPanelRoute = {gt::kMaxN, "one workgroup holds the generator", kNH2D, kNUpdate, kNSums, kNCov, kND2H, panel_bytes, reserve_panel, panel_solve};
+const Route kBlockedRoute = {GSUM_TOEP_BLOCKED_MAX_N, "the grids of the panel kernels", kBH2D, kBUpdate, kBSums, kBCov, kBD2H, blocked_bytes, reserve_blocked,
+                             blocked_solve};
+
+// The body of gsum_toep_gram_panel and gsum_toep_gram_blocked (`who`).
+void gram_route(const char* who, const Route& r, gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols,
+                double* G_out, double* sld_out, int32_t* info_out) {
+    const std::string name(who);
+    if (!h || !t || !Z || !G_out || !sld_out || !info_out) throw Error(name + ": null pointer argument");
+    if (m < 1 || n < 1 || n_sets < 1)
+        throw Error(name + ": m, n and n_sets must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n) + ", " + std::to_string(n_sets));
+    check_cols(who, cols);
+    check_order(who, n, r.max_n, r.why);
+    check_sets(who, n, n_sets, cols);
+    check_scale(who, t, m, n, " and G and sum_log_diag with it");
+    const int ncols = (int)(n_sets * cols);
+    const size_t per_theta = (size_t)n * ncols;
+    const int64_t step = columns_per_launch(m, r.bytes(n, ncols), kPanelBudget);
+    const size_t gsz = (size_t)n_sets * cols * cols;
+    run(h, [&] {
+        h->t.reserve((size_t)m * n);
+        h->Z.reserve(per_theta);
+        r.reserve(h, n, ncols, step);
+        h->G.reserve(gsz * m);
+        h->sld.reserve((size_t)m);
+        h->info.reserve((size_t)m);
+        h->ze.reserve((size_t)ncols);
+        hipStream_t st = h->stream;
+        timed(h, r.h2d, [&] {
+            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
+        });
+        timed(h, r.prepare, [&] { launch_colexp(h, (int)n, ncols); });
+        for (int64_t lo = 0; lo < m; lo += step) {
+            const int64_t cnt = std::min(step, m - lo);
+            int32_t* il = h->info.p + lo;
+            r.solve(h, h->t.p + lo * n, (int)n, ncols, cnt, h->sld.p + lo, il);
+            timed(h, r.sums, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
+        }
+        timed(h, r.d2h, [&] { read_back(h, m, gsz, G_out, sld_out, info_out); });
+    });
+}
+
+// The body of gsum_toep_predict_panel and gsum_toep_predict_blocked (`who`).
+void predict_route(const char* who, const Route& r, gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c,
+                   double* quad_out, double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out) {
+    const std::string name(who);
+    if (!h || !t || !K || !quad_out || !sld_out || !info_out) throw Error(name + ": null pointer argument");
+    if (q < 1 || n < 1) throw Error(name + ": n and q must be >= 1, got " + std::to_string(n) + ", " + std::to_string(q));
+    if (c < 0 || c > gt::kMaxCols) throw Error(name + ": c must be between 0 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(c));
+    if (c > 0 && (!Z || !cross_out || !G_out)) throw Error(name + ": null pointer argument (Z, cross_out and G_out with c > 0)");
+    check_order(who, n, r.max_n, r.why);
+    if (q > (((int64_t)1 << 31) - 1) / n - c)
+        throw Error(name + ": n * (q + c) must be < 2^31, got " + std::to_string(n) + " x (" + std::to_string(q) + " + " + std::to_string(c) + ")");
+    if (cov_out && q > 16 * 65535) throw Error(name + ": cov_out takes q <= 1048560, got " + std::to_string(q));
+    check_scale(who, t, 1, n, " and the outputs with it");
+    const int ncols = (int)(q + c), qi = (int)q;
+    const size_t ny = (size_t)n * ncols;
+    run(h, [&] {
+        h->t.reserve((size_t)n);
+        h->Z.reserve(ny);
+        r.reserve(h, n, ncols, 1);
+        h->ze.reserve((size_t)ncols);
+        h->sld.reserve(1);
+        h->info.reserve(1);
+        h->quad.reserve((size_t)q);
+        if (c) {
+            h->cross.reserve((size_t)q * c);
+            h->Yz.reserve((size_t)n * c);
+            h->G.reserve((size_t)c * c);
+        }
+        if (cov_out) h->cov.reserve((size_t)q * q);
+        hipStream_t st = h->stream;
+        timed(h, r.h2d, [&] {
+            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(h->Z.p, K, sizeof(double) * n * q, hipMemcpyHostToDevice, st));
+            if (c) SL_CHECK(hipMemcpyAsync(h->Z.p + (size_t)n * q, Z, sizeof(double) * n * c, hipMemcpyHostToDevice, st));
+        });
+        timed(h, r.prepare, [&] { launch_colexp(h, (int)n, ncols); });
+        r.solve(h, h->t.p, (int)n, ncols, 1, h->sld.p, h->info.p);
+        timed(h, r.sums, [&] {
+            gt::k_pred_sums<<<dim3((unsigned)q, (unsigned)(1 + c)), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->quad.p, h->cross.p);
+            SL_LAUNCHED("k_pred_sums");
+            if (c) {                                                           // the residual columns alone, as one set of k_gram's
+                SL_CHECK(hipMemcpy2DAsync(h->Yz.p, sizeof(double) * c, h->Y.p + q, sizeof(double) * ncols, sizeof(double) * c, (size_t)n,
+                                          hipMemcpyDeviceToDevice, st));
+                gt::k_gram<<<dim3((unsigned)c, 1, 1), gt::kWave, 0, st>>>(h->Yz.p, (int)n, c, 1, h->ze.p + q, h->info.p, h->G.p);
+                SL_LAUNCHED("k_gram");
+            }
+        });
+        if (cov_out)
+            timed(h, r.cov, [&] {
+                const unsigned tiles = (unsigned)((q + 15) / 16);
+                gt::k_pred_cov<<<dim3(tiles, tiles), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->cov.p);
+                SL_LAUNCHED("k_pred_cov");
+            });
+        timed(h, r.d2h, [&] {
+            SL_CHECK(hipMemcpyAsync(quad_out, h->quad.p, sizeof(double) * q, hipMemcpyDeviceToHost, st));
+            if (c) {
+                SL_CHECK(hipMemcpyAsync(cross_out, h->cross.p, sizeof(double) * q * c, hipMemcpyDeviceToHost, st));
+                SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * c * c, hipMemcpyDeviceToHost, st));
+            }
+            if (cov_out) SL_CHECK(hipMemcpyAsync(cov_out, h->cov.p, sizeof(double) * q * q, hipMemcpyDeviceToHost, st));
+            SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double), hipMemcpyDeviceToHost, st));
+            SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        });
+    });
 }
 
 }  // namespace
@@ -520,108 +715,13 @@ GT_API int32_t gsum_toep_panel_width(const gsum_toep*) { return gt::kPanelB; }
 
 GT_API int gsum_toep_gram_panel(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
                                 double* sld_out, int32_t* info_out) {
-    return guarded([&] {
-        if (!h || !t || !Z || !G_out || !sld_out || !info_out) throw Error("gsum_toep_gram_panel: null pointer argument");
-        if (m < 1 || n < 1 || n_sets < 1)
-            throw Error("gsum_toep_gram_panel: m, n and n_sets must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n) + ", " + std::to_string(n_sets));
-        check_cols("gsum_toep_gram_panel", cols);
-        check_order("gsum_toep_gram_panel", n);
-        check_sets("gsum_toep_gram_panel", n, n_sets, cols);
-        check_scale("gsum_toep_gram_panel", t, m, n, " and G and sum_log_diag with it");
-        const int ncols = (int)(n_sets * cols);
-        const size_t per_theta = (size_t)n * ncols;
-        const int64_t step = columns_per_launch(m, panel_bytes(n, ncols), kPanelBudget);
-        const size_t gsz = (size_t)n_sets * cols * cols;
-        run(h, [&] {
-            h->t.reserve((size_t)m * n);
-            h->Z.reserve(per_theta);
-            reserve_panel(h, n, ncols, step);
-            h->G.reserve(gsz * m);
-            h->sld.reserve((size_t)m);
-            h->info.reserve((size_t)m);
-            h->ze.reserve((size_t)ncols);
-            hipStream_t st = h->stream;
-            timed(h, kNH2D, [&] {
-                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
-                SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
-            });
-            timed(h, kNUpdate, [&] { launch_colexp(h, (int)n, ncols); });
-            for (int64_t lo = 0; lo < m; lo += step) {
-                const int64_t cnt = std::min(step, m - lo);
-                int32_t* il = h->info.p + lo;
-                panel_solve(h, h->t.p + lo * n, (int)n, ncols, cnt, h->sld.p + lo, il);
-                timed(h, kNSums, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
-            }
-            timed(h, kND2H, [&] { read_back(h, m, gsz, G_out, sld_out, info_out); });
-        });
-    });
+    return guarded([&] { gram_route("gsum_toep_gram_panel", kPanelRoute, h, t, m, n, Z, n_sets, cols, G_out, sld_out, info_out); });
 }
 
 GT_API int gsum_toep_predict_panel(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c,
                                    double* quad_out, double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out) {
     return guarded([&] {
-        if (!h || !t || !K || !quad_out || !sld_out || !info_out) throw Error("gsum_toep_predict_panel: null pointer argument");
-        if (q < 1 || n < 1) throw Error("gsum_toep_predict_panel: n and q must be >= 1, got " + std::to_string(n) + ", " + std::to_string(q));
-        if (c < 0 || c > gt::kMaxCols)
-            throw Error("gsum_toep_predict_panel: c must be between 0 and " + std::to_string(gt::kMaxCols) + ", got " + std::to_string(c));
-        if (c > 0 && (!Z || !cross_out || !G_out)) throw Error("gsum_toep_predict_panel: null pointer argument (Z, cross_out and G_out with c > 0)");
-        check_order("gsum_toep_predict_panel", n);
-        if (q > (((int64_t)1 << 31) - 1) / n - c)
-            throw Error("gsum_toep_predict_panel: n * (q + c) must be < 2^31, got " + std::to_string(n) + " x (" + std::to_string(q) + " + " + std::to_string(c) + ")");
-        if (cov_out && q > 16 * 65535) throw Error("gsum_toep_predict_panel: cov_out takes q <= 1048560, got " + std::to_string(q));
-        check_scale("gsum_toep_predict_panel", t, 1, n, " and the outputs with it");
-        const int ncols = (int)(q + c), qi = (int)q;
-        const size_t ny = (size_t)n * ncols;
-        run(h, [&] {
-            h->t.reserve((size_t)n);
-            h->Z.reserve(ny);
-            reserve_panel(h, n, ncols, 1);
-            h->ze.reserve((size_t)ncols);
-            h->sld.reserve(1);
-            h->info.reserve(1);
-            h->quad.reserve((size_t)q);
-            if (c) {
-                h->cross.reserve((size_t)q * c);
-                h->Yz.reserve((size_t)n * c);
-                h->G.reserve((size_t)c * c);
-            }
-            if (cov_out) h->cov.reserve((size_t)q * q);
-            hipStream_t st = h->stream;
-            timed(h, kNH2D, [&] {
-                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * n, hipMemcpyHostToDevice, st));
-                SL_CHECK(hipMemcpyAsync(h->Z.p, K, sizeof(double) * n * q, hipMemcpyHostToDevice, st));
-                if (c) SL_CHECK(hipMemcpyAsync(h->Z.p + (size_t)n * q, Z, sizeof(double) * n * c, hipMemcpyHostToDevice, st));
-            });
-            timed(h, kNUpdate, [&] { launch_colexp(h, (int)n, ncols); });
-            panel_solve(h, h->t.p, (int)n, ncols, 1, h->sld.p, h->info.p);
-            timed(h, kNSums, [&] {
-                gt::k_pred_sums<<<dim3((unsigned)q, (unsigned)(1 + c)), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->quad.p,
-                                                                                          h->cross.p);
-                SL_LAUNCHED("k_pred_sums");
-                if (c) {                                                       // the residual columns alone, as one set of k_gram's
-                    SL_CHECK(hipMemcpy2DAsync(h->Yz.p, sizeof(double) * c, h->Y.p + q, sizeof(double) * ncols, sizeof(double) * c, (size_t)n,
-                                              hipMemcpyDeviceToDevice, st));
-                    gt::k_gram<<<dim3((unsigned)c, 1, 1), gt::kWave, 0, st>>>(h->Yz.p, (int)n, c, 1, h->ze.p + q, h->info.p, h->G.p);
-                    SL_LAUNCHED("k_gram");
-                }
-            });
-            if (cov_out)
-                timed(h, kNCov, [&] {
-                    const unsigned tiles = (unsigned)((q + 15) / 16);
-                    gt::k_pred_cov<<<dim3(tiles, tiles), gt::kWave, 0, st>>>(h->Y.p, (int)n, qi, c, h->ze.p, h->info.p, h->cov.p);
-                    SL_LAUNCHED("k_pred_cov");
-                });
-            timed(h, kND2H, [&] {
-                SL_CHECK(hipMemcpyAsync(quad_out, h->quad.p, sizeof(double) * q, hipMemcpyDeviceToHost, st));
-                if (c) {
-                    SL_CHECK(hipMemcpyAsync(cross_out, h->cross.p, sizeof(double) * q * c, hipMemcpyDeviceToHost, st));
-                    SL_CHECK(hipMemcpyAsync(G_out, h->G.p, sizeof(double) * c * c, hipMemcpyDeviceToHost, st));
-                }
-                if (cov_out) SL_CHECK(hipMemcpyAsync(cov_out, h->cov.p, sizeof(double) * q * q, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(sld_out, h->sld.p, sizeof(double), hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            });
-        });
+        predict_route("gsum_toep_predict_panel", kPanelRoute, h, t, n, K, q, Z, c, quad_out, cross_out, cov_out, G_out, sld_out, info_out);
     });
 }
 
@@ -629,5 +729,28 @@ GT_API int gsum_toep_panel_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_panel_times: null pointer argument");
         read_times(h, kEveryPhase, kTotalPhases - kEveryPhase, ms, reset);
+    });
+}
+
+GT_API int64_t gsum_toep_blocked_max_n(const gsum_toep*) { return GSUM_TOEP_BLOCKED_MAX_N; }
+
+GT_API int32_t gsum_toep_blocked_tile_rows(const gsum_toep*) { return gt::kTileR; }
+
+GT_API int gsum_toep_gram_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
+                                  double* sld_out, int32_t* info_out) {
+    return guarded([&] { gram_route("gsum_toep_gram_blocked", kBlockedRoute, h, t, m, n, Z, n_sets, cols, G_out, sld_out, info_out); });
+}
+
+GT_API int gsum_toep_predict_blocked(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c,
+                                     double* quad_out, double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out) {
+    return guarded([&] {
+        predict_route("gsum_toep_predict_blocked", kBlockedRoute, h, t, n, K, q, Z, c, quad_out, cross_out, cov_out, G_out, sld_out, info_out);
+    });
+}
+
+GT_API int gsum_toep_blocked_times(gsum_toep* h, double* ms, int32_t reset) {
+    return guarded([&] {
+        if (!h || !ms) throw Error("gsum_toep_blocked_times: null pointer argument");
+        read_times(h, kTotalPhases, kGrandPhases - kTotalPhases, ms, reset);
     });
 }

@@ -28,6 +28,9 @@
 // The panel route (the comments stand at the kernels): k_schur_panel runs k_schur's step without residual columns
 //   and writes L in panels, k_panel_diag solves a panel's triangular block for every right-hand side, k_panel_update applies the
 //   panel to the rows below on the fp64 MFMA, k_panel_load lays the scaled right-hand sides out row-major.
+// The blocked route (the comments stand at the kernels): k_schur_lead runs a panel's steps on the rows under the
+//   pivot and hands out their (rho, 1 / c), k_schur_tiles replays them on every row, tile by tile, from one state buffer in HBM
+//   into another, and writes the panel; k_blocked_init forms the state, k_blocked_sld sums the logarithms of the diagonal.
 // Every value is written with ordinary vector stores; there are no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1023,6 +1026,220 @@ __global__ __launch_bounds__(kWave) void k_panel_update(const double* __restrict
             Ct[(int64_t)row * ncols + col] = zc[t][r];
         }
     }
+}
+
+// ---- the blocked route ------------------------------------------------------------------------------------------
+// A step of the recursion is local: u'[i] and v'[i] need u[i-1], v[i] and the step's (rho, 1 / c), and those need u[k] and v[k+1]
+// alone.  So a panel of kPanelB steps splits into a serial lead on the kPanelB + 1 rows under the pivot, which yields the panel's
+// coefficients and info (k_schur_lead, one wave per first column), and a replay of those coefficients on every row at or below the
+// pivot, tile by tile (k_schur_tiles, one wave per tile): a tile owns kTileR rows and loads kPanelB more above them, which is as far
+// up as kPanelB steps reach, so what its halo lacks never arrives in its own rows.  The generator state lives in HBM, (4, n) doubles
+// per first column (u.h, u.l, v.h, v.l), twice: the tiles of a panel read one buffer, halo included, and write the other.  Nothing
+// holds a whole generator, so n is bounded by the grids and the indices alone.  Every element goes through the expressions of
+// k_schur_panel's step in its order; the panel is stored in its layout, and k_panel_diag and k_panel_update consume it unchanged.
+// Kernels follow one another in stream order; no workgroup waits for another.
+
+constexpr int kTileE = 8;                          // generator elements per lane of a tile
+constexpr int kTileSpan = kWave * kTileE;          // rows a tile loads
+constexpr int kTileR = kTileSpan - kPanelB;        // rows a tile owns
+constexpr int kLeadE = (kPanelB + 1 + kWave - 1) / kWave;      // window elements per lane of the lead: row k0 + e * 64 + lane
+// What the kernels rely on: the halo (kPanelB rows) and at least a wave of own rows fit the tile's span, the halo is whole lanes
+// (a lane is all halo or all own rows), and the lead's window fits its lanes.  Tile and panel boundaries need not line up: the
+// tiles of a panel start at the tile that holds row k0, wherever k0 falls in it.
+static_assert(kTileR >= kWave && kPanelB % kTileE == 0 && kPanelB + 1 <= kLeadE * kWave, "the halo, the own rows and the lead's window fit their lanes");
+
+// The generator state of every first column from t, as k_schur_panel forms it at k0 == 0, and info = 1 for a bad t[0] (0 otherwise).
+// grid = (ceil(n / 256), m), block = 256.
+__global__ __launch_bounds__(256) void k_blocked_init(const double* __restrict__ t, int n, double* __restrict__ st, int32_t* __restrict__ info) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int64_t theta = blockIdx.y;
+    const double* tt = t + theta * n;
+    const double t0 = tt[0];
+    const int bad = (t0 > 0.0 && t0 < INFINITY) ? 0 : 1;
+    if (i == 0) info[theta] = bad;
+    if (bad || i >= n) return;
+    const dd rs = dd_rsqrt(dd{t0, 0.0});
+    const dd u = dd_mul_d(rs, tt[i]);
+    const dd v = i > 0 ? u : dd{0.0, 0.0};
+    double* s = st + theta * 4 * (int64_t)n;
+    s[i] = u.h;
+    s[(int64_t)n + i] = u.l;
+    s[2 * (int64_t)n + i] = v.h;
+    s[3 * (int64_t)n + i] = v.l;
+}
+
+// The steps k0 .. min(k0 + kPanelB, n - 1) - 1 of every first column on the rows k0 .. min(k0 + kPanelB, n - 1) of its state st:
+// k_schur_panel's expressions for rho, the failure test and 1 / c, and its rotation of the window's rows below the pivot.  Lane l
+// holds the rows k0 + l, k0 + 64 + l, ..; the pivot pair and the element shifted in from the row above come by lane shuffles.  Step k
+// stores {rho.h, rho.l, ic.h, ic.l} at coef[theta, k - k0]; a failure at step k sets info[theta] = k + 2 and ends the first column,
+// which this and every later kernel then skips.  grid = m, block = kWave.
+__global__ __launch_bounds__(kWave) void k_schur_lead(int n, int k0, const double* __restrict__ st, double* __restrict__ coef,
+                                                       int32_t* __restrict__ info) {
+    const int lane = threadIdx.x;
+    const int64_t theta = blockIdx.x;
+    if (info[theta] != 0) return;                                             // the same in every lane
+    const double* s = st + theta * 4 * (int64_t)n;
+    double* co = coef + theta * 4 * kPanelB;
+    const int last = min(k0 + kPanelB, n - 1);                                // the last row of the window
+    double uh[kLeadE], ul[kLeadE], vh[kLeadE], vl[kLeadE];
+#pragma unroll
+    for (int e = 0; e < kLeadE; ++e) {
+        const int i = k0 + e * kWave + lane;
+        const bool in = i <= last;
+        uh[e] = in ? s[i] : 0.0;
+        ul[e] = in ? s[(int64_t)n + i] : 0.0;
+        vh[e] = in ? s[2 * (int64_t)n + i] : 0.0;
+        vl[e] = in ? s[3 * (int64_t)n + i] : 0.0;
+    }
+    int bad = 0;
+    for (int k = k0; k < last; ++k) {
+        const int wu = k - k0, wv = wu + 1;                                   // the window rows of u[k] and v[k + 1]
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+        for (int e = 0; e < kLeadE; ++e) {
+            a0 = (wu >> 6) == e ? uh[e] : a0;
+            a1 = (wu >> 6) == e ? ul[e] : a1;
+            a2 = (wv >> 6) == e ? vh[e] : a2;
+            a3 = (wv >> 6) == e ? vl[e] : a3;
+        }
+        const dd pu = {__shfl(a0, wu & 63, kWave), __shfl(a1, wu & 63, kWave)};
+        const dd pv = {__shfl(a2, wv & 63, kWave), __shfl(a3, wv & 63, kWave)};
+        const dd rho = dd_div(pv, pu);
+        if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every lane
+            bad = k + 2;
+            break;
+        }
+        const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
+        const dd nrho = dd_neg(rho);
+        if (lane == 0) {
+            co[4 * wu] = rho.h;
+            co[4 * wu + 1] = rho.l;
+            co[4 * wu + 2] = ic.h;
+            co[4 * wu + 3] = ic.l;
+        }
+#pragma unroll
+        for (int e = kLeadE - 1; e >= 0; --e) {
+            const int i = k0 + e * kWave + lane;
+            // u shifted down by one: the row above is the lane before, or lane 63 of the slot before
+            double sh = __shfl(uh[e], (lane + kWave - 1) & 63, kWave), sl = __shfl(ul[e], (lane + kWave - 1) & 63, kWave);
+            const double ph = e > 0 ? __shfl(uh[e > 0 ? e - 1 : 0], kWave - 1, kWave) : 0.0;
+            const double pl = e > 0 ? __shfl(ul[e > 0 ? e - 1 : 0], kWave - 1, kWave) : 0.0;
+            const dd us = lane == 0 ? dd{ph, pl} : dd{sh, sl};
+            const dd v = {vh[e], vl[e]};
+            const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
+            const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+            const bool live = i > k && i <= last;                             // at or above the pivot: u[i] keeps L[i, i]
+            uh[e] = live ? un.h : uh[e];
+            ul[e] = live ? un.l : ul[e];
+            vh[e] = live ? vn.h : vh[e];
+            vl[e] = live ? vn.l : vl[e];
+        }
+    }
+    if (bad && lane == 0) info[theta] = bad;
+}
+
+// The panel k0 .. k1 - 1 (k1 = min(k0 + kPanelB, n)) on the rows of one tile, replaying the coefficients of k_schur_lead.  Tile
+// k0 / kTileR + blockIdx.x owns the rows r0 .. r0 + kTileR - 1 (r0 a multiple of kTileR) and loads from `cur` the rows from
+// r0 - kPanelB on, kTileE consecutive ones per lane in registers; the element a shift brings over a lane boundary comes by a lane
+// shuffle, so a step has no barrier and no LDS.  For each k the tile stores its own rows >= k of column k of L (u before the
+// rotation) as k_schur_panel does, Ph[theta, k - k0, i] and (float) of the low word in Pl, the owner of row k also hi(L_kk) in
+// dg[theta, k]; then it rotates every element it holds, u only below the pivot.  After s steps the first s rows of the halo are
+// stale; the own rows lie kPanelB below its top and stay exact.  At the end it writes its own rows to `nxt`.
+// Rows above the pivot are unspecified in both state buffers and never used: v is rotated and stored there too (as k_schur does),
+// tiles above the pivot's are not launched, so their rows of `nxt` keep what an earlier panel left, and the pivot tile's halo reads
+// such rows of `cur`.  All of that reaches only u[i-1] and v[i] of rows i <= k, which no rotation below the pivot takes.
+// grid = (tiles from the pivot's on, cnt), block = kWave.
+__global__ __launch_bounds__(kWave) void k_schur_tiles(int n, int k0, const double* __restrict__ cur, double* __restrict__ nxt,
+                                                        const double* __restrict__ coef, double* __restrict__ Ph, float* __restrict__ Pl,
+                                                        double* __restrict__ dg, const int32_t* __restrict__ info) {
+    const int64_t theta = blockIdx.y;
+    if (info[theta] != 0) return;                                             // the same in every lane
+    const int lane = threadIdx.x;
+    const int r0 = (k0 / kTileR + (int)blockIdx.x) * kTileR;                  // the tile's first own row
+    const int base = r0 - kPanelB + lane * kTileE;                            // the row of the lane's first element
+    const double* s = cur + theta * 4 * (int64_t)n;
+    double* so = nxt + theta * 4 * (int64_t)n;
+    const double* co = coef + theta * 4 * kPanelB;
+    double* ph = Ph + theta * (int64_t)kPanelB * n;
+    float* pl = Pl + theta * (int64_t)kPanelB * n;
+    double* d = dg + theta * n;
+    double uh[kTileE], ul[kTileE], vh[kTileE], vl[kTileE];
+#pragma unroll
+    for (int e = 0; e < kTileE; ++e) {
+        const int i = base + e;
+        const bool in = i >= 0 && i < n;
+        uh[e] = in ? s[i] : 0.0;
+        ul[e] = in ? s[(int64_t)n + i] : 0.0;
+        vh[e] = in ? s[2 * (int64_t)n + i] : 0.0;
+        vl[e] = in ? s[3 * (int64_t)n + i] : 0.0;
+    }
+    const int k1 = min(k0 + kPanelB, n);
+    for (int k = k0; k < k1; ++k) {
+        double* pk = ph + (int64_t)(k - k0) * n;
+        float* qk = pl + (int64_t)(k - k0) * n;
+#pragma unroll
+        for (int e = 0; e < kTileE; ++e) {                                    // column k of L, the tile's own rows k .. n - 1
+            const int i = base + e;
+            if (i >= r0 && i >= k && i < n) {
+                pk[i] = uh[e];
+                qk[i] = (float)ul[e];
+                if (i == k) d[k] = uh[e];
+            }
+        }
+        if (k == n - 1) break;
+        const double* ck = co + 4 * (k - k0);
+        const dd nrho = {-ck[0], -ck[1]}, ic = {ck[2], ck[3]};
+        const double eh = __shfl_up(uh[kTileE - 1], 1, kWave), el = __shfl_up(ul[kTileE - 1], 1, kWave);
+        const dd edge = lane > 0 ? dd{eh, el} : dd{0.0, 0.0};
+#pragma unroll
+        for (int e = kTileE - 1; e >= 0; --e) {
+            const int i = base + e;
+            const dd us = e > 0 ? dd{uh[e > 0 ? e - 1 : 0], ul[e > 0 ? e - 1 : 0]} : edge;          // u shifted down by one
+            const dd v = {vh[e], vl[e]};
+            const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
+            const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+            const bool live = i > k;                                          // at or above the pivot: u[i] keeps L[i, i]
+            uh[e] = live ? un.h : uh[e];
+            ul[e] = live ? un.l : ul[e];
+            vh[e] = vn.h;
+            vl[e] = vn.l;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < kTileE; ++e) {
+        const int i = base + e;
+        if (i >= r0 && i < n) {
+            so[i] = uh[e];
+            so[(int64_t)n + i] = ul[e];
+            so[2 * (int64_t)n + i] = vh[e];
+            so[3 * (int64_t)n + i] = vl[e];
+        }
+    }
+}
+
+// sld[theta] = sum_j log dg[theta, j] in k_schur's order: thread tid adds the logarithms of its E consecutive entries in ascending
+// order, then the binary tree over the threads; NaN for a first column that failed.  With E the size class of n (n <= kMaxN) this is
+// k_schur's sum bit for bit; beyond, E = ceil(n / kThreads).  grid = m, block = kThreads.
+__global__ __launch_bounds__(kThreads) void k_blocked_sld(const double* __restrict__ dg, int n, int E, double* __restrict__ sld,
+                                                           const int32_t* __restrict__ info) {
+    __shared__ double red[kThreads];
+    const int tid = threadIdx.x;
+    const int64_t theta = blockIdx.x;
+    const int bad = info[theta];                                              // the same in every thread
+    const double* d = dg + theta * n;
+    double s = 0.0;
+    if (!bad) {
+        const int64_t base = (int64_t)tid * E;
+        for (int e = 0; e < E; ++e)
+            if (base + e < n) s += log(d[base + e]);
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
+        if (tid < stride) red[tid] += red[tid + stride];
+        __syncthreads();
+    }
+    if (tid == 0) sld[theta] = bad ? NAN : red[0];
 }
 
 }  // namespace gt

@@ -99,12 +99,14 @@ def toeplitz_column(kernel, X, nugget=0.0, device=None, backend=None):
     return column_of_desc(_context(device, backend), desc, X, nugget)
 
 
-def toeplitz_max_n(backend=None):
-    """The largest n ``toeplitz_gram`` takes: the device's limit (one workgroup holds a generator); none on ``backend='cpu'``."""
+def toeplitz_max_n(backend=None, method="columns"):
+    """The largest n ``toeplitz_gram`` and ``toeplitz_predict`` take with ``method``: the device's limit (one workgroup holds a
+    generator; with ``method="blocked"`` the grids of its kernels); none on ``backend='cpu'``."""
+    check_method(method)
     if resolve_backend(backend) == "cpu":
         return None
     from . import _toep_lib
-    return _toep_lib.max_n()
+    return _toep_lib.max_n(method)
 
 
 def _cpu_gram(t, Z, n_sets, steps=None):
@@ -225,7 +227,10 @@ def toeplitz_gram(t, Z, n_sets=1, device=None, backend=None, method="columns"):
     further few; ``method="panel"`` runs one recursion per first column in panels of
     ``toeplitz_panel_width()`` columns of L and applies each panel to all columns at once on the matrix unit: the schedule for many
     sets.  Same arithmetic per entry, cut into panels: G agrees to the accuracy of either, ``sum_log_diag`` and ``info`` bit for
-    bit.  ``backend='cpu'`` has one code for both."""
+    bit.  ``method="blocked"`` splits each panel's recursion into a serial lead on the rows under the pivot
+    and tiles that replay its coefficients on all rows at once, with the generator in device memory: bit for bit the panel route's
+    results, and the one schedule beyond ``toeplitz_max_n()``, up to ``toeplitz_max_n(method="blocked")``.  ``backend='cpu'`` has
+    one code for all three."""
     check_method(method)
     t2, single = _first_columns(t)
     Z, n_sets, cols = _rhs_sets(Z, t2.shape[1], n_sets)
@@ -481,7 +486,8 @@ def toeplitz_predict(t, K, Z=None, want_cov=False, chunk=None, device=None, back
     Nothing n x n is formed: the columns ride the forward substitution of the Schur recursion.  ``chunk`` is the largest number of
     new points per device call (default ``predict_chunk(n, c)``); the results do not depend on it bit for bit.  ``want_cov`` needs all
     q points in one call: ValueError, naming the limit, otherwise.  Where ``info`` is not 0 every array is NaN.
-    ``method="panel"``: all columns of a call ride one recursion (``toeplitz_gram``); ``chunk`` then only bounds the memory."""
+    ``method="panel"``: all columns of a call ride one recursion (``toeplitz_gram``); ``chunk`` then only bounds the memory.
+    ``method="blocked"``: the panel route's results from the tiled recursion, for n up to ``toeplitz_max_n(method="blocked")``."""
     check_method(method)
     t = np.asarray(t, dtype=float)
     if t.ndim != 1 or t.size < 1:

@@ -108,6 +108,35 @@
  * gsum_toep_panel_times: ms[0..6] = device milliseconds spent by the two in: 0 host-to-device copies, 1 the recursion, 2 the
  *   triangular blocks, 3 the trailing updates (with the scaling of the right-hand sides), 4 the sums G, quad and cross, 5 cov,
  *   6 device-to-host copies.  The other three clocks are not charged by them.
+ *
+ * The blocked route (opt-in; the entry points above are unchanged, and they keep refusing n > gsum_toep_max_n).  On the panel route one
+ * workgroup still holds a whole generator and runs its recursion alone.  But a step is local -- u'[i] and v'[i] need u[i-1], v[i] and
+ * the step's (rho, 1 / c), which need u[k] and v[k+1] alone -- so the B steps of a panel split into a lead, one wave per first column
+ * that runs them on the B + 1 rows under the pivot and yields the B coefficient pairs and info, and tiles: one wave per R =
+ * gsum_toep_blocked_tile_rows() rows, which loads its rows and a halo of B rows above them, replays the coefficients, stores its
+ * rows of the panel's columns of L and its rows of the next state.  The state lives in device memory, two buffers of 4 n doubles
+ * per first column, read from one and written to the other.  Every element sees the expressions of the panel route in its order,
+ * and the panel is consumed by the panel route's own triangular block and trailing update: for n <= gsum_toep_max_n every output is
+ * bit for bit that of the panel entry points.  Nothing holds a whole generator, so n is bounded by the grids alone.  Nothing n x n
+ * is stored: one panel (12 n B bytes), the right-hand sides (12 bytes an entry) and 9 n + 4 B doubles per first column in flight.
+ *
+ * gsum_toep_blocked_max_n: the largest n the two entry points below take, GSUM_TOEP_BLOCKED_MAX_N (the trailing update's grid).  h may
+ *   be NULL.
+ *
+ * gsum_toep_blocked_tile_rows: R, a compile-time constant of the library.  h may be NULL.
+ *
+ * gsum_toep_gram_blocked: the arguments, outputs and refusals of gsum_toep_gram_panel, with n <= gsum_toep_blocked_max_n in place
+ *   of gsum_toep_max_n.  The first columns go through in chunks that keep their solved columns, panels, states, coefficients and
+ *   diagonals within 1 GiB.  sum_log_diag is summed in the order of the entry points above, which for n > gsum_toep_max_n continues
+ *   as ceil(n / 512) consecutive entries per thread of 512, then the binary tree: fixed by n alone.
+ *
+ * gsum_toep_predict_blocked: the arguments, outputs and refusals of gsum_toep_predict_panel, with the same limit on n.  The caller
+ *   bounds the device memory: 12 n (q + c + B) bytes and q * q doubles with cov_out.
+ *
+ * gsum_toep_blocked_times: ms[0..7] = device milliseconds spent by the two in: 0 host-to-device copies, 1 the leads, 2 the tiles (with
+ *   the formation of the state and the sum of the logarithms), 3 the triangular blocks, 4 the trailing updates (with the scaling of
+ *   the right-hand sides), 5 the sums G, quad and cross, 6 cov, 7 device-to-host copies.  The other four clocks are not charged by
+ *   them.
  */
 #ifndef GSUM_TOEP_H
 #define GSUM_TOEP_H
@@ -119,6 +148,7 @@ extern "C" {
 
 #define GSUM_TOEP_MAX_N 8192
 #define GSUM_TOEP_MAX_COLS 16
+#define GSUM_TOEP_BLOCKED_MAX_N 1048576
 
 typedef struct gsum_toep gsum_toep;
 
@@ -145,6 +175,13 @@ int gsum_toep_gram_panel(gsum_toep* h, const double* t, int64_t m, int64_t n, co
 int gsum_toep_predict_panel(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
                             double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out);
 int gsum_toep_panel_times(gsum_toep* h, double* ms, int32_t reset);
+int64_t gsum_toep_blocked_max_n(const gsum_toep* h);
+int32_t gsum_toep_blocked_tile_rows(const gsum_toep* h);
+int gsum_toep_gram_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t n_sets, int32_t cols, double* G_out,
+                           double* sld_out, int32_t* info_out);
+int gsum_toep_predict_blocked(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
+                              double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out);
+int gsum_toep_blocked_times(gsum_toep* h, double* ms, int32_t reset);
 
 #ifdef __cplusplus
 }
