@@ -228,6 +228,7 @@ PROTOTYPES = {
 LAB_PROTOTYPES = {
     "gsum_debug_pipe_probe": (C.c_int, [_p, C.c_int32, C.POINTER(C.c_int32)]),
     "gsum_debug_diag_stamps": (C.c_int, [_p, _ip]),
+    "gsum_debug_wave_factor": (C.c_int, [_p, C.c_int32, _dp, _ip]),
     "gsum_debug_chain_stamps": (C.c_int, [_p, _dp, C.c_int32, C.POINTER(C.c_int32)]),
     "gsum_probe_mfma_f64": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "gsum_probe_hbm_write": (C.c_int, [_p, C.c_int64, _dp]),
@@ -787,15 +788,28 @@ class HipContext:
         out = out[: steps.value]
         return np.where(out < 0, np.nan, out * 0.01)
 
+    def wave_factor(self, eval_index: int) -> np.ndarray:
+        """The augmented workspace matrix (np + 16 square) the last grouped batch call left for its evaluation ``eval_index`` (lab build)."""
+        order = np.zeros(1, dtype=np.int64)
+        self._check(self._lib.gsum_debug_wave_factor(self._h, int(eval_index), None, order.ctypes.data_as(_ip)))
+        out = np.empty((int(order[0]), int(order[0])))
+        self._check(self._lib.gsum_debug_wave_factor(self._h, int(eval_index), _ptr(out), order.ctypes.data_as(_ip)))
+        return out
+
     PROFILE_CLASSES = ("kernel_build", "diag_block", "panel_gemm", "bulk_update", "other")
 
     def kernel_profile(self):
         """Per kernel class {name: dict(ms, flops, launches)} of the launches profiled since the last read-out (option
-        "profile_gemm" = N: every launch of every N-th fused evaluation); resets the record."""
+        "profile_gemm" = N: every launch of every N-th fused evaluation); resets the record.  ``bulk_update`` also carries ``tiles`` and
+        ``tiles_run``: the far-update tiles the profiled batch calls launched and how many of them had something to subtract (option
+        "wave_skip_zero": a tile whose operand panels are exactly zero returns at once).  ``flops`` stays the dense algorithmic count."""
         ms, fl, cnt = np.zeros(5), np.zeros(5), np.zeros(5, dtype=np.int64)
+        tiles, tiles_run = (int(self._lib.gsum_get_option(self._h, k)) for k in (b"bulk_tiles", b"bulk_tiles_run"))
         self._check(self._lib.gsum_kernel_profile(self._h, _ptr(ms), _ptr(fl), cnt.ctypes.data_as(_ip)))
-        return {name: dict(ms=float(ms[i]), flops=float(fl[i]), launches=int(cnt[i]))
+        prof = {name: dict(ms=float(ms[i]), flops=float(fl[i]), launches=int(cnt[i]))
                 for i, name in enumerate(self.PROFILE_CLASSES)}
+        prof["bulk_update"].update(tiles=tiles, tiles_run=tiles_run)
+        return prof
 
     def pipe_probe(self, extra: int = 0) -> np.ndarray:
         """(4 + extra)^2 matrix of pairwise overlaps (fraction of a 100-us kernel) of the context's four streams and ``extra``

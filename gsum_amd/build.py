@@ -36,7 +36,7 @@ KERNEL_PARTS = ("common", "build", "diag", "panel", "chain", "gemm_nt", "fused",
 DEPS = [SRC, os.path.join(HERE, "csrc", "gsum_kernels.hip.h"), os.path.join(ROOT, "include", "gsum_hip.h"),
         os.path.join(ROOT, "include", "gsum_hip_debug.h")] + [os.path.join(HERE, "csrc", "kernels", f"{p}.hip.h") for p in KERNEL_PARTS]
 HOST_PARTS = ("context", "gemm", "matrices", "potrf", "api_context", "api_operators", "pstrf", "api_fused", "wave", "api_lml", "api_multi", "api_grad", "api_measure")
-DEPS += [os.path.join(HERE, "csrc", "host", f"{p}.hip.h") for p in HOST_PARTS]
+DEPS += [os.path.join(HERE, "csrc", "host", f"{p}.hip.h") for p in HOST_PARTS] + [os.path.join(HERE, "csrc", "kernels", "zwin.h")]
 OUT = os.path.join(HERE, "libgsum_hip.so")
 OUT_LAB = os.path.join(HERE, "libgsum_hip_lab.so")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-fvisibility=hidden", "-pthread",

@@ -24,6 +24,7 @@
 // The kernels live in kernels/*.hip.h, included here in dependency order (one translation unit: gsum_capi.hip).
 #pragma once
 #include "kernels/common.hip.h"
+#include "kernels/zwin.h"
 #include "kernels/build.hip.h"
 #include "kernels/diag.hip.h"
 #include "kernels/panel.hip.h"

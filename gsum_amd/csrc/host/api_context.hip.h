@@ -159,6 +159,7 @@ void gsum_destroy(gsum_ctx* ctx) {
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->pscratch) (void)hipFree(ctx->pscratch);
     if (ctx->panel_stats) (void)hipFree(ctx->panel_stats);
+    if (ctx->prof_tiles_run) (void)hipFree(ctx->prof_tiles_run);
     if (ctx->hbatch) (void)hipHostFree(ctx->hbatch);
     if (ctx->gws) (void)hipFree(ctx->gws);
     if (ctx->dstamps) (void)hipFree(ctx->dstamps);
@@ -174,6 +175,15 @@ int64_t gsum_get_option(gsum_ctx* ctx, const char* name) {
     if (!strcmp(name, "wave_streams")) return ctx->wave_last_streams;     // streams the last batch call used (groups + 1; 0: none yet)
     if (!strcmp(name, "wave_groups")) return ctx->wave_groups;
     if (!strcmp(name, "wave_size")) return ctx->wave_size;
+    if (!strcmp(name, "wave_skip_zero")) return ctx->wave_skip_zero;
+    if (!strcmp(name, "bulk_tiles")) return ctx->prof_tiles;                 // far-update tiles of the profiled batch calls: launched ...
+    if (!strcmp(name, "bulk_tiles_run")) {                                  // ... and with something to subtract (synchronises)
+        unsigned h = 0;
+        if (!ctx->prof_tiles_run) return 0;
+        if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(&h, ctx->prof_tiles_run, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return (int64_t)h;
+    }
     if (!strcmp(name, "lookahead")) return ctx->lookahead;
     if (!strcmp(name, "chain_persist")) return ctx->chain_persist;
     if (!strcmp(name, "chain_probe")) return ctx->chain_probe;          // 0 not run, 1 streams concurrent, -1 serialised
@@ -322,6 +332,7 @@ int gsum_set_option(gsum_ctx* ctx, const char* name, int64_t value) {
     }
     else if (!strcmp(name, "wave_groups")) ctx->wave_groups = (int)std::max<int64_t>(1, std::min<int64_t>(GS_WV_STREAM_GROUPS, value));
     else if (!strcmp(name, "wave_size")) ctx->wave_size = (int)std::max<int64_t>(1, std::min<int64_t>(GS_WVC_MAX, value));
+    else if (!strcmp(name, "wave_skip_zero")) ctx->wave_skip_zero = value != 0;
     else {
 #ifdef GSUM_LAB
         return gs_set_option_lab(ctx, name, value);

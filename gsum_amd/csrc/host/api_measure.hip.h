@@ -71,6 +71,22 @@ int gsum_debug_diag_stamps(gsum_ctx* ctx, int64_t* out64) {
     return 0;
 }
 
+int gsum_debug_wave_factor(gsum_ctx* ctx, int32_t eval, double* out, int64_t* order) {
+    if (!ctx || !order) return -2;
+    GS_CHECK(hipSetDevice(ctx->device));
+    GS_CHECK(hipDeviceSynchronize());
+    for (int gi = 0; gi < GS_WV_GROUPS; ++gi) {
+        const gs_wave_group* g = &ctx->wave.g[gi];
+        if (!g->cap || eval < g->first_eval || eval >= g->first_eval + g->cnt) continue;
+        const int64_t naug = g->pool.np + GS_BORDER;
+        *order = naug;
+        if (out) GS_CHECK(hipMemcpy2D(out, (size_t)naug * sizeof(double), g->pool.A + (int64_t)(eval - g->first_eval) * g->pool.strideA,
+                                      (size_t)g->pool.ld * sizeof(double), (size_t)naug * sizeof(double), (size_t)naug, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    GS_FAIL("gsum_debug_wave_factor: no group workspace holds that evaluation");
+}
+
 #endif  // GSUM_LAB
 
 int gsum_kernel_profile(gsum_ctx* ctx, double* ms5, double* flops5, int64_t* launches5) {
@@ -90,6 +106,8 @@ int gsum_kernel_profile(gsum_ctx* ctx, double* ms5, double* flops5, int64_t* lau
     }
     ctx->prof_recs.clear();
     ctx->prof_next = 0;
+    ctx->prof_tiles = 0;
+    if (ctx->prof_tiles_run) GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, sizeof(unsigned)));
     return 0;
 }
 

@@ -224,6 +224,12 @@ struct gsum_ctx {
     int wave_groups = 3;             // groups = chain streams; their bulk launches alternate on ONE bulk stream (4 streams: the HIP runtime's
                                      // default number of hardware queues)
     int wave_size = 8;               // evaluations per group at most
+    int wave_skip_zero = 1;          // the panel solves flag their 16-row groups that are not all +-0, leave all-zero rows alone, and the trailing-update
+                                     // tiles multiply only the span of operand panels in which their rows of A and of B are flagged (kernels/zwin.h):
+                                     // on a banded kernel matrix (a short length scale on a long grid) nearly every tile returns at once.  0: null flag
+                                     // pointers everywhere -- the dense launches.  Same G, sum log L_ii, info and factor (zeros may differ in sign)
+    unsigned* prof_tiles_run = nullptr;   // diagnostics (profile_gemm): far-update tiles of the batch schedule that multiplied, counted on the device ...
+    int64_t prof_tiles = 0;               // ... of this many launched (gsum_get_option "bulk_tiles_run" / "bulk_tiles"; gsum_kernel_profile resets both)
     int wave_tile128_rows = 0;       // far updates of at least this many rows on the 128 x 128 workgroup tile (k_gemm_ld3g2); 0 (default): never.  Alone the
                                      // tile is +2.7 % at M = 15120 and +1.5 % at 11280; inside a batch it LOSES (profiles/r05_tile128.log: n = 16384 45.4
                                      // against 45.6 evals/s, n = 12288 104.6 / 105.3, n = 8192 from 6144 rows 327.8 / 333.7): two 66-KB workgroups of

@@ -17,7 +17,7 @@
 // (same kernels' bodies, same K = 256 / K = 512 pairing of the trailing updates): G, sum log L_ii and info are bit-identical to it.
 static void gs_wave_free_group(gs_wave_group* g) {
     for (void* q : {(void*)g->pool.A, (void*)g->pool.Ltab, (void*)g->pool.Lsib, (void*)g->pool.logdet, (void*)g->pool.diag0,
-                    (void*)g->pool.info, (void*)g->pool.res})
+                    (void*)g->pool.info, (void*)g->pool.res, (void*)g->pool.zfl})
         if (q) (void)hipFree(q);
     memset(&g->pool, 0, sizeof g->pool);
     g->cap = 0;
@@ -42,7 +42,7 @@ static void gs_wave_release(gsum_ctx* ctx, bool streams) {
 static double gs_wave_ws_bytes(int64_t np) {
     const double T = (double)(np / GS_NB);
     return (double)(np + GS_BORDER) * (double)GS_LD(np) * 8.0 + T * GS_LTAB * 8.0 + (T / 2 + 1) * GS_LSIB * 8.0 +
-           (T + (double)np + (double)GS_RES_LEN) * 8.0 + 4.0;
+           (T + (double)np + (double)GS_RES_LEN) * 8.0 + 4.0 + (double)(np / (2 * GS_NB)) * (double)((np + GS_BORDER) / 16);
 }
 
 // G groups in all, the first Gs of them with a chain stream of their own; group i >= Gs (a second cohort) runs on group (i - Gs)'s
@@ -91,6 +91,8 @@ static int gs_wave_prepare(gsum_ctx* ctx, int G, int B, int64_t n, int64_t np, i
         if (e == hipSuccess) e = hipMalloc((void**)&p.diag0, (size_t)B * np * sizeof(double));
         if (e == hipSuccess) e = hipMalloc((void**)&p.info, (size_t)B * sizeof(int));
         if (e == hipSuccess) e = hipMalloc((void**)&p.res, (size_t)B * GS_RES_LEN * sizeof(double));
+        // (never cleared: every flag a trailing update reads was written by a panel solve of the same round, see gs_panel256_body)
+        if (e == hipSuccess) e = hipMalloc((void**)&p.zfl, (size_t)B * (size_t)(np / (2 * GS_NB)) * (size_t)((np + GS_BORDER) / 16));
         if (e != hipSuccess) {
             gs_wave_free_group(g);
             ctx->err = std::string("hipMalloc(group workspaces) failed: ") + hipGetErrorString(e);
@@ -127,10 +129,10 @@ static void gs_wave_bulk_plan(int64_t np, int depth, int64_t deep_min_rows, int 
     }
 }
 
-static int gs_wave_fill_chain(const gs_wave_group* g, gs_wv_chain_args* a, bool panel_counts) {
+static int gs_wave_fill_chain(const gs_wave_group* g, gs_wv_chain_args* a, bool panel_counts, bool skip_zero = false) {
     a->p = g->pool;
     a->n = g->cnt;
-    a->pad = 0;
+    a->zon = skip_zero ? 1 : 0;
     const int naug = g->pool.np + GS_BORDER;
     int run = 0;
     for (int e = 0; e < g->cnt; ++e) {
@@ -234,6 +236,10 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
     }
     const bool prof = ctx->profile_gemm > 0;
     if (prof) ctx->prof_this_eval = true;
+    if (prof && !ctx->prof_tiles_run) {
+        GS_CHECK(hipMalloc((void**)&ctx->prof_tiles_run, sizeof(unsigned)));
+        GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, sizeof(unsigned)));
+    }
     // everything of this call follows what the context's main stream has done so far (the resident inputs' upload)
     hipStream_t s0 = ctx->slots[0].sm;
     GS_CHECK(hipEventRecord(ctx->slots[0].evFork, s0));
@@ -294,7 +300,7 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 }
                 {
                     hipStream_t spn = serial ? wv->sb : g->run;
-                    const int groups = gs_wave_fill_chain(g, &ca, true);
+                    const int groups = gs_wave_fill_chain(g, &ca, true, ctx->wave_skip_zero != 0);
                     const int rec = gs_prof_begin(ctx, spn, GS_PROF_PANEL, (double)g->cnt * 4.0 * (double)mrest * GS_NB * GS_NB);
                     if (ctx->wave_panel_wg4 == 8) hipLaunchKernelGGL(k_panel256gw<8>, dim3((unsigned)((groups + 7) / 8)), dim3(512), 0, spn, ca);
                     else if (ctx->wave_panel_wg4 && ctx->wave_panel_rows_lds) hipLaunchKernelGGL((k_panel256gw<4, true>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, spn, ca);
@@ -328,7 +334,7 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 en.N = st.near ? 2 * GS_NB : (int)mrest;
                 en.K = st.K;
                 en.tri = st.near ? 0 : 1;
-                en.pad = 0;
+                en.first = st.first;
                 const int64_t tm = (mrest + 127) / 128;
                 // large lower triangles on the 128 x 128 tile (round 5; alone +2.7 % at M = 15120, +1.5 % at 11280, -7 % on ONE matrix at 7184:
                 // profiles/r05_tile128.log), far updates on the bulk stream only
@@ -343,6 +349,16 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                     run += tiles;
                     ga.end[e] = run;
                 }
+                // The zero flags of panels first .. step, rows from r2 on: written by this round's panel solves, which are ahead of this launch on
+                // the chain stream (or behind evChain on the bulk stream).  Off (wave_skip_zero = 0): null, every tile multiplies its whole K.
+                ga.zfl = ctx->wave_skip_zero ? g->pool.zfl : nullptr;
+                ga.zstride = (int64_t)S * (naug / 16);
+                ga.zps = (int)(naug / 16);
+                ga.zg = (int)(r2 / 16);
+                // diagnostics (profile_gemm): tiles of the far updates that have something to subtract, counted on the device, beside the tiles
+                // launched (less the one tile past the last column that the plain grid of a small triangle carries)
+                ga.zrun = (prof && !near) ? ctx->prof_tiles_run : nullptr;
+                if (ga.zrun) ctx->prof_tiles += (int64_t)g->cnt * (tiles - ((en.tri && !big_tile && !gs_tri_shifted(en.M) && (en.M - 1) % 128 < 64) ? 1 : 0));
                 const int rec = gs_prof_begin(ctx, su, near ? GS_PROF_PANEL : GS_PROF_BULK, fl * g->cnt);     // (near updates on the bulk stream: the same kernel, the same class)
                 const size_t shm = 2 * (size_t)((128 + (big_tile ? 128 : 64)) * GS_KC + 4) * sizeof(double);
                 if (big_tile && !ctx->lds_attr_done.count((const void*)k_gemm_ld3g2)) {

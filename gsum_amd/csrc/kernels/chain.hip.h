@@ -103,9 +103,22 @@ __global__ __launch_bounds__(64) void k_probe_wait(const unsigned* f, const unsi
 // rows [0, M) x 256 columns at P: both panels of an outer step in one launch, 16 rows per single-wave workgroup:
 //   X_j = B_j L_jj^-T;   B_j+1 -= X_j L(j+1, j)^T;   X_j+1 = B_j+1 L_j+1,j+1^-T
 // (k_panel, the K = 128 sibling update on k_gemm_nt, k_panel again -- without two launches and two passes over the rows)
+// zflag (the batch schedule, option wave_skip_zero; null everywhere else): this row group's zero flag.  The wave writes 1 there when any
+// of the 16 x 256 entries it leaves in the matrix has bits other than +-0 (NaN and Inf count) and 0 otherwise -- every group of a
+// launch writes its byte, so nothing is cleared and nothing is stale when a workspace is used again -- and the trailing updates skip
+// the operand panels whose rows are unflagged (kernels/zwin.h).  With it a half that is all +-0 as loaded is left alone: rows that
+// are zero in the panel's columns solve to zero, and X_j = 0 takes nothing from B_j+1.
+__device__ __forceinline__ bool gs_panel16_any(const gs_d4 (&P)[8]) {              // wave-uniform: some entry is not +-0
+    unsigned long long u = 0ull;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int x = 0; x < 4; ++x) u |= (unsigned long long)__double_as_longlong(P[k][x]);
+    return __ballot((u << 1) != 0ull) != 0ull;
+}
 __device__ __forceinline__ void gs_panel256_body(double* P, int64_t ld, int M, const double* Ltab0, const double* Lsib,
                                                  const double* Ltab1, unsigned long long* kst, unsigned long long* wstat, const int group,
-                                                 double* tile = nullptr) {
+                                                 double* tile = nullptr, unsigned char* zflag = nullptr) {
     const int lane = threadIdx.x & 63;
     const int r0 = group * 16;
     if (r0 >= M) return;
@@ -115,14 +128,23 @@ __device__ __forceinline__ void gs_panel256_body(double* P, int64_t ld, int M, c
     double* rows = P + (int64_t)r0 * ld;
     gs_d4 P0[8], P1[8];
     if (tile) gs_panel16_load_t(P0, rows, ld, M - r0, lane, tile); else gs_panel16_load(P0, rows, ld, M - r0, lane);
-    gs_panel16_solve_g(P0, Ltab0, lane);
-    if (tile) gs_panel16_store_t(P0, rows, ld, M - r0, lane, tile); else gs_panel16_store(P0, rows, ld, M - r0, lane);
+    const bool live0 = !zflag || gs_panel16_any(P0);
+    bool any = false;
+    if (live0) {
+        gs_panel16_solve_g(P0, Ltab0, lane);
+        if (tile) gs_panel16_store_t(P0, rows, ld, M - r0, lane, tile); else gs_panel16_store(P0, rows, ld, M - r0, lane);
+        if (zflag) any = gs_panel16_any(P0);
+    }
     __builtin_amdgcn_sched_barrier(0);          // the second 128 columns are fetched only now: 64 registers less at the peak
     if (tile) gs_panel16_load_t(P1, rows + 128, ld, M - r0, lane, tile); else gs_panel16_load(P1, rows + 128, ld, M - r0, lane);
-    gs_sib_update_lean(P1, P0, Lsib, lane);
+    if (live0) gs_sib_update_lean(P1, P0, Lsib, lane);
     __builtin_amdgcn_sched_barrier(0);
-    gs_panel16_solve_g(P1, Ltab1, lane);
-    if (tile) gs_panel16_store_t(P1, rows + 128, ld, M - r0, lane, tile); else gs_panel16_store(P1, rows + 128, ld, M - r0, lane);
+    if (live0 || gs_panel16_any(P1)) {
+        gs_panel16_solve_g(P1, Ltab1, lane);
+        if (tile) gs_panel16_store_t(P1, rows + 128, ld, M - r0, lane, tile); else gs_panel16_store(P1, rows + 128, ld, M - r0, lane);
+        if (zflag) any = any || gs_panel16_any(P1);
+    }
+    if (zflag && lane == 0) *zflag = any ? 1 : 0;
     if (kst && lane == 0) atomicMax(kst + 1, __builtin_amdgcn_s_memrealtime());
     if (wstat && lane == 0) {                                   // diagnostics (option panel_stats): how long the panel's waves are resident
         atomicAdd(wstat, __builtin_amdgcn_s_memrealtime() - w_t0);
@@ -250,10 +272,16 @@ struct gs_wv_pool {
     int* info;                               // 1 per workspace
     double* res;                             // one result record per workspace (k_finalize_g)
     int np, T;
+    unsigned char* zfl;                      // zero flags of the solved panels, (np / 256) x ((np + 16) / 16) bytes per workspace (kernels/zwin.h)
 };
+// a panel launch's flag for 16-row group `group` below outer step `step` of workspace q; null with option wave_skip_zero off (a.zon)
+__device__ __forceinline__ unsigned char* gs_wv_zflag(const gs_wv_pool& p, bool on, int64_t q, int step, int64_t r2, int group) {
+    const int64_t ps = (p.np + GS_BORDER) / 16;
+    return on ? p.zfl + (q * (p.np / (2 * GS_NB)) + step) * ps + r2 / 16 + group : nullptr;
+}
 struct gs_wv_chain_args {
     gs_wv_pool p;
-    int n, pad;
+    int n, zon;                              // zon: the panel solves write (and use) the zero flags
     short q[GS_WVC_MAX], step[GS_WVC_MAX];
     int end[GS_WVC_MAX];                     // k_panel256g: running counts of 16-row groups
 };
@@ -278,7 +306,8 @@ __global__ __launch_bounds__(64, 2) void k_panel256g(const gs_wv_chain_args a) {
     const int M = a.p.np + GS_BORDER - (int)r2;
     gs_panel256_body(a.p.A + q * a.p.strideA + r2 * a.p.ld + c0, a.p.ld, M, a.p.Ltab + (q * a.p.T + b) * GS_LTAB,
                      a.p.Lsib + (q * (a.p.T / 2 + 1) + b / 2) * GS_LSIB, a.p.Ltab + (q * a.p.T + b + 1) * GS_LTAB,
-                     (unsigned long long*)nullptr, (unsigned long long*)nullptr, bid - first);
+                     (unsigned long long*)nullptr, (unsigned long long*)nullptr, bid - first, (double*)nullptr,
+                     gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, bid - first));
 }
 // The same with W = 4 (or 8) waves per workgroup, each on its own 16-row group.  Single-wave workgroups are spread round-robin
 // over the CUs, and one 224-register panel wave on a SIMD is enough to keep a whole bulk workgroup (2 waves on EACH of the CU's 4
@@ -299,7 +328,8 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void k_panel256gw(const gs_
     gs_panel256_body(a.p.A + q * a.p.strideA + r2 * a.p.ld + c0, a.p.ld, M, a.p.Ltab + (q * a.p.T + b) * GS_LTAB,
                      a.p.Lsib + (q * (a.p.T / 2 + 1) + b / 2) * GS_LSIB, a.p.Ltab + (q * a.p.T + b + 1) * GS_LTAB,
                      (unsigned long long*)nullptr, (unsigned long long*)nullptr, grp - first,
-                     TR ? tiles + (threadIdx.x >> 6) * GS_PT_TILE : (double*)nullptr);
+                     TR ? tiles + (threadIdx.x >> 6) * GS_PT_TILE : (double*)nullptr,
+                     gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, grp - first));
 }
 // entering evaluations: border rows <- RHS^T (k_set_border), grid ((np + 16) / 256 rounded up, entries)
 struct gs_wv_zsets { int64_t off[GS_WVC_MAX]; };         // per entry: offset (doubles) of its right-hand-side set in Z

@@ -66,6 +66,16 @@ __host__ __device__ inline unsigned gs_tri_second(int64_t M, int c2) {       // 
     return cnt;
 }
 
+// The grouped launches' flag view (kernels/zwin.h; null: the whole K range, every launch outside the batch schedule): the tile multiplies
+// only the span of 256-column operand panels in which some 16-row group of ITS rows of A and some group of ITS rows of B are flagged
+// nonzero, and a tile with no such panel returns before it has touched memory or a barrier -- C -= (exact zeros) leaves C as it is.
+struct gs_zwin_view {
+    const unsigned char* fl;       // the member's flags, [outer step][16-row group of the augmented matrix]; null: no window
+    unsigned* run;                 // diagnostics (profile_gemm): counts the tiles that multiply; null otherwise
+    int first, pstride;            // the operand's first panel (outer step); flags per outer step
+    int gA, gB;                    // row-group index of row 0 of A / of B (rows are multiples of 16 from there)
+};
+
 // BNT = 1: the 128 x 64 workgroup tile (8 waves of 32 x 32, 63 registers, three workgroups per CU) -- every launch of rounds 2-4.
 // BNT = 2 (round 5): 128 x 128 (8 waves of 64 x 32: WM = 4, 2 waves down x 4 across; ~100 registers, 66 KB of LDS, two workgroups per CU): 0.75
 // LDS reads and 0.125 LDS-direct loads per MFMA instead of 1 and 0.1875, a third fewer operand bytes per flop.  Same k order per accumulator:
@@ -74,7 +84,7 @@ template <int NST, int BNT = 1>
 __device__ __forceinline__ void gs_gemm_ld3_body(double* C, int64_t ldc, const double* A, int64_t lda, const double* B,
                                                  int64_t ldb, int M, int N, int K, int tri, int beta, double sign,
                                                  unsigned long long* kst, int nfirst, unsigned* first_done, const int bid_in,
-                                                 const int c2 = 0, unsigned* second_done = nullptr) {
+                                                 const int c2 = 0, unsigned* second_done = nullptr, const gs_zwin_view* zv = nullptr) {
     constexpr int WM = BNT == 2 ? 4 : 2, WN = 2, WAVES_M = BNT == 2 ? 2 : 4, BM = 128, BN = 64 * BNT;
     static_assert(BNT == 1 || (BNT == 2 && NST == 2), "the 128 x 128 tile exists with two LDS stages only");
     constexpr int OPA = BM * GS_KC + 2, OPB = BN * GS_KC + 2, STAGE = OPA + OPB;
@@ -225,6 +235,26 @@ __device__ __forceinline__ void gs_gemm_ld3_body(double* C, int64_t ldc, const d
         A += m0;
         B += m0;
         K -= m0;
+    }
+    if (zv && tri != 2) {
+        if (zv->fl) {
+            // The tile's rows of A are [m0, min(m0 + BM, Mr)), of B [n0, min(n0 + BN, N)): whole 16-row groups (M, N and the shifted grid's
+            // offset are multiples of 16 in the batch schedule).  Every wave reads the same flags, written by launches that have ended, and
+            // the ballot makes the window a scalar: the decision is uniform over the workgroup.
+            const int nA = ((m0 + BM < Mr ? BM : Mr - m0) + 15) >> 4, nB = ((n0 + BN < N ? BN : N - n0) + 15) >> 4;
+            const int gA0 = zv->gA + (m0 >> 4), gB0 = zv->gB + (n0 >> 4), nP = K / 256;
+            int lo = -1, hi = -1;
+            for (int j0 = 0; j0 < nP; j0 += GS_ZW_PASS) {
+                const int64_t idx = gs_zwin_slot(lane, zv->first + j0, zv->first + nP, zv->pstride, gA0, nA, gB0, nB);
+                const unsigned char f = idx >= 0 ? zv->fl[idx] : (unsigned char)0;
+                gs_zwin_scan(__ballot(f != 0), j0, nP, &lo, &hi);
+            }
+            if (lo < 0) return;               // nothing to subtract: no load, no barrier, C untouched
+            A += 256 * lo;
+            B += 256 * lo;
+            K = 256 * (hi - lo);
+        }
+        if (zv->run && t == 0) atomicAdd(zv->run, 1u);
     }
     const int fr = lane & 15, fq = lane >> 4;
     const bool neg = sign < 0.0;
@@ -502,14 +532,22 @@ __global__ __launch_bounds__(512, 4) void k_gemm_ld3b(double* C, int64_t ldc, co
 struct gs_wv_gemm_entry {
     int64_t offC, offA, offB;      // doubles from the evaluation's workspace base
     int M, N, K, tri;
-    int q, pad;                    // workspace index within the group
+    int q, first;                  // workspace index within the group; the operand's first panel (outer step: the flag view's)
 };
 struct gs_wv_gemm_args {
     double* base; int64_t strideA, ld;
     int n, pad;
     int end[GS_WV_MAX];            // running tile counts: entry e owns block ids [end[e - 1], end[e])
     gs_wv_gemm_entry e[GS_WV_MAX];
+    // the zero flags of the panel solves (option wave_skip_zero; gs_zwin_view): workspace q's flags start zstride bytes after workspace
+    // q - 1's, zps per outer step; zg: row-group index of the operands' row 0 (A and B start at the same row of the matrix)
+    const unsigned char* zfl; unsigned* zrun;
+    int64_t zstride;
+    int zps, zg;
 };
+__device__ __forceinline__ gs_zwin_view gs_wv_zview(const gs_wv_gemm_args& a, const gs_wv_gemm_entry& en) {
+    return gs_zwin_view{a.zfl ? a.zfl + (int64_t)en.q * a.zstride : nullptr, a.zrun, en.first, a.zps, a.zg, a.zg};
+}
 __device__ __forceinline__ void gs_gemm_ld3g_body(const gs_wv_gemm_args& a) {
     const int bid = (int)blockIdx.x;
     int e = 0;
@@ -517,8 +555,9 @@ __device__ __forceinline__ void gs_gemm_ld3g_body(const gs_wv_gemm_args& a) {
     const int first = e ? a.end[e - 1] : 0;
     const gs_wv_gemm_entry& en = a.e[e];
     double* W = a.base + (int64_t)en.q * a.strideA;
+    const gs_zwin_view zv = gs_wv_zview(a, en);
     gs_gemm_ld3_body<2>(W + en.offC, a.ld, W + en.offA, a.ld, W + en.offB, a.ld, en.M, en.N, en.K, en.tri, 1, -1.0,
-                        (unsigned long long*)nullptr, 0, (unsigned*)nullptr, bid - first);
+                        (unsigned long long*)nullptr, 0, (unsigned*)nullptr, bid - first, 0, (unsigned*)nullptr, &zv);
 }
 // k_gemm_ld3g: the big ("far") trailing updates, one after the other on the batch schedule's bulk stream.  k_gemm_ld3n: the same
 // code under a name of its own for the small "near" updates that run on the groups' chain streams BESIDE them -- so that a
@@ -531,8 +570,9 @@ __device__ __forceinline__ void gs_gemm_ld3g_body_t(const gs_wv_gemm_args& a) {
     const int first = e ? a.end[e - 1] : 0;
     const gs_wv_gemm_entry& en = a.e[e];
     double* W = a.base + (int64_t)en.q * a.strideA;
+    const gs_zwin_view zv = gs_wv_zview(a, en);
     gs_gemm_ld3_body<2, BNT>(W + en.offC, a.ld, W + en.offA, a.ld, W + en.offB, a.ld, en.M, en.N, en.K, en.tri, 1, -1.0,
-                             (unsigned long long*)nullptr, 0, (unsigned*)nullptr, bid - first);
+                             (unsigned long long*)nullptr, 0, (unsigned*)nullptr, bid - first, 0, (unsigned*)nullptr, &zv);
 }
 // the far updates of large trailing matrices on the 128 x 128 tile (option wave_tile128_rows)
 __global__ __launch_bounds__(512, 4) void k_gemm_ld3g2(const gs_wv_gemm_args a) { gs_gemm_ld3g_body_t<2>(a); }

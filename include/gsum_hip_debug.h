@@ -28,6 +28,9 @@ extern "C" {
  * round-2 kernel: [7] start, [8 + 2j], [9 + 2j] wave 0 behind the two barriers of micro-block column j, [24 + j] cycles
  * of the pivot recurrence of micro-block j). */
 int gsum_debug_diag_stamps(gsum_ctx* ctx, int64_t* out64);
+/* the augmented workspace matrix ((np + 16)^2 doubles, row-major; lower triangle = the factor, the right-hand-side rows below it) that the
+ * last grouped batch call left for its evaluation `eval` -- what gsum_lml_grad_batch reads.  *order = np + 16; out == NULL: the order only. */
+int gsum_debug_wave_factor(gsum_ctx* ctx, int32_t eval, double* out, int64_t* order);
 /* the pairwise stream probe of gsum_init (option "pipes_ok") on the context's four streams plus `extra` (0..4) streams created for the
  * call: out = (4 + extra)^2 overlaps of the pairs' two 100-us kernels in 1/1000 of their length (diagonal 1000).  A pair on one
  * command-processor pipe takes turns (~0); DESIGN.md section 4.1. */
