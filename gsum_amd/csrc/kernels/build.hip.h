@@ -35,9 +35,15 @@ __device__ __constant__ double gs_exp_tl[16] = {
     -0x1.3b3efbf5e2228p-54, -0x1.b32dcb94da51dp-56, 0x1.db72fc1f0eab4p-55, 0x1.1affc2b91ce27p-56,
     0x1.c1a7792cb3387p-55, 0x1.36eae30af0cb3p-56, 0x1.4a385a63d07a7p-56, -0x1.ff7128fd391f0p-55};
 
-__device__ __forceinline__ double gs_exp_np(double x) {
+// The one definition of that arithmetic is gs_exp_core (every constant is written once, which
+// tests/test_exp_restatement.py asserts); the entry points below differ only in where the 2^(j/16) table lives
+// (th / tl: LDS in the build kernels, __constant__ in the gradient and tree paths) and in what they do outside
+// the table algorithm's range.
+#define GS_EXP_INRANGE 0x1.61da04cbafe44p+9            // |x| below this (707.7): the table algorithm
+
+// |x| < GS_EXP_INRANGE only: no range test here
+__device__ __forceinline__ double gs_exp_core(double x, const double* th, const double* tl) {
 #pragma clang fp contract(off)
-    if (!(fabs(x) < 0x1.61da04cbafe44p+9)) return exp(x);
     const double L2E = 0x1.71547652b82fep+0, SH = 0x1.8000000003ff0p+48;
     const double L2H = 0x1.62e42fefa39efp-1, L2L = 0x1.abc9e3b39803fp-56;
     // M = RZ(x*L2E + SH): round-toward-zero of a positive sum = floor on the 1/16 grid.  Emulated with a
@@ -46,57 +52,7 @@ __device__ __forceinline__ double gs_exp_np(double x) {
     const double nn = t - SH;
     const double dd = __builtin_fma(x, L2E, -nn);
     const double N = dd < 0.0 ? nn - 0.0625 : nn;
-    const long long k16 = (long long)(N * 16.0);
-    const int j = (int)(k16 & 15);
-    double R = __builtin_fma(-N, L2H, x);
-    R = __builtin_fma(-N, L2L, R);
-    const double R2 = R * R;
-    const double pA = __builtin_fma(0x1.7411836940c04p-10, R, 0x1.1101cbbc265c0p-7);
-    const double pB = __builtin_fma(0x1.55557242d68fep-5, R, 0x1.5555553939732p-3);
-    const double pC = __builtin_fma(0x1.000000000d008p-1, R, 0x1.fffffffffff70p-1);
-    double pp = __builtin_fma(R2, pA, pB);
-    pp = __builtin_fma(R2, pp, pC);
-    const double q = __builtin_fma(pp, R, gs_exp_tl[j]);
-    const double th = gs_exp_th[j];
-    const double res = __builtin_fma(th, q, th);
-    return ldexp(res, (int)(k16 >> 4));
-}
-
-__device__ __forceinline__ double gs_base_value(int family, double s) {
-#pragma clang fp contract(off)
-    if (family == GSUM_RBF) return gs_exp_np(-0.5 * s);
-    double dist = sqrt(s);
-    if (family == GSUM_MATERN52) {
-        double t = dist * 2.23606797749979;      // math.sqrt(5)
-        return (1.0 + t + (t * t) / 3.0) * gs_exp_np(-t);
-    }
-    if (family == GSUM_MATERN32) {
-        double t = dist * 1.7320508075688772;    // math.sqrt(3)
-        return (1.0 + t) * gs_exp_np(-t);
-    }
-    return gs_exp_np(-dist);
-}
-
-
-// ---- second version of the kernel build (round 2) ---------------------------------------------------------------
-// The first version was bound by instruction issue, not by HBM: a runtime switch over the kernel family and a runtime
-// loop over the input dimensions inside the per-entry loop, the 2^(j/16) table read through divergent global loads from
-// constant memory, a 64-bit float -> integer conversion, and diagonal / padding tests on every entry: ~90 VALU
-// instructions per entry, 89 us for the 34 M entries of the n = 8192 lower triangle (3.1 TB/s of stores).  Here the
-// family and the one-dimensional case are template parameters, the table lives in LDS, the exponent goes through
-// v_cvt_i32_f64, tiles that touch neither the diagonal nor the padding skip every test, and a workgroup takes 32 x 128
-// entries (8320 tiles at n = 8192: 4 rounds of the 2048 resident workgroups instead of 1.02 with a one-tile tail).
-// Same arithmetic, operation for operation (array_equal to scikit-learn is asserted on the device for every family).
-__device__ __forceinline__ double gs_exp_np_t(double x, const double* th, const double* tl) {
-#pragma clang fp contract(off)
-    if (!(fabs(x) < 0x1.61da04cbafe44p+9)) return exp(x);
-    const double L2E = 0x1.71547652b82fep+0, SH = 0x1.8000000003ff0p+48;
-    const double L2H = 0x1.62e42fefa39efp-1, L2L = 0x1.abc9e3b39803fp-56;
-    const double t = __builtin_fma(x, L2E, SH);
-    const double nn = t - SH;
-    const double dd = __builtin_fma(x, L2E, -nn);
-    const double N = dd < 0.0 ? nn - 0.0625 : nn;
-    const int k16 = (int)(N * 16.0);                      // |N| < 1022: exact in 32 bits
+    const int k16 = (int)(N * 16.0);                      // |N| < 1022: exact in 32 bits (v_cvt_i32_f64)
     const int j = k16 & 15;
     double R = __builtin_fma(-N, L2H, x);
     R = __builtin_fma(-N, L2L, R);
@@ -112,71 +68,72 @@ __device__ __forceinline__ double gs_exp_np_t(double x, const double* th, const 
     return ldexp(res, k16 >> 4);
 }
 
-template <int FAM>
-__device__ __forceinline__ double gs_base_value_t(double s, const double* th, const double* tl) {
-#pragma clang fp contract(off)
-    if (FAM == GSUM_RBF) return gs_exp_np_t(-0.5 * s, th, tl);
-    const double dist = sqrt(s);
-    if (FAM == GSUM_MATERN52) {
-        const double t = dist * 2.23606797749979;      // math.sqrt(5)
-        return (1.0 + t + (t * t) / 3.0) * gs_exp_np_t(-t, th, tl);
-    }
-    if (FAM == GSUM_MATERN32) {
-        const double t = dist * 1.7320508075688772;    // math.sqrt(3)
-        return (1.0 + t) * gs_exp_np_t(-t, th, tl);
-    }
-    return gs_exp_np_t(-dist, th, tl);
+__device__ __forceinline__ double gs_exp_np_t(double x, const double* th, const double* tl) {
+    if (!(fabs(x) < GS_EXP_INRANGE)) return exp(x);
+    return gs_exp_core(x, th, tl);
 }
+
+__device__ __forceinline__ double gs_exp_np(double x) { return gs_exp_np_t(x, gs_exp_th, gs_exp_tl); }
 
 // Branch-free form for the build kernel's inner loop.  Two argument ranges need no table arithmetic at all:
 //   x < -745.2       exp(x) is exactly 0.0 in fp64 (below half the smallest denormal) -- on a grid with dx = 0.5 l that
 //                    is every entry more than 39 length scales from the diagonal, i.e. most of a large matrix;
-//   |x| < 707.7      the table algorithm (gs_exp_np_t's fast path).
+//   |x| < 707.7      the table algorithm (gs_exp_core).
 // What is left (the band -745.2 <= x <= -707.7 where the result is a denormal, overflow, NaN) is flagged and recomputed
 // by the caller with the library exp, wave-uniformly, so that the common paths carry no per-entry branch.
 __device__ __forceinline__ double gs_exp_np_nobranch(double x, const double* th, const double* tl, bool& slow) {
-#pragma clang fp contract(off)
     const bool far = x < -745.2;
-    const bool inr = fabs(x) < 0x1.61da04cbafe44p+9;
+    const bool inr = fabs(x) < GS_EXP_INRANGE;
     slow = !(far || inr);
-    const double xs = inr ? x : 0.0;
-    const double L2E = 0x1.71547652b82fep+0, SH = 0x1.8000000003ff0p+48;
-    const double L2H = 0x1.62e42fefa39efp-1, L2L = 0x1.abc9e3b39803fp-56;
-    const double t = __builtin_fma(xs, L2E, SH);
-    const double nn = t - SH;
-    const double dd = __builtin_fma(xs, L2E, -nn);
-    const double N = dd < 0.0 ? nn - 0.0625 : nn;
-    const int k16 = (int)(N * 16.0);
-    const int j = k16 & 15;
-    double R = __builtin_fma(-N, L2H, xs);
-    R = __builtin_fma(-N, L2L, R);
-    const double R2 = R * R;
-    const double pA = __builtin_fma(0x1.7411836940c04p-10, R, 0x1.1101cbbc265c0p-7);
-    const double pB = __builtin_fma(0x1.55557242d68fep-5, R, 0x1.5555553939732p-3);
-    const double pC = __builtin_fma(0x1.000000000d008p-1, R, 0x1.fffffffffff70p-1);
-    double pp = __builtin_fma(R2, pA, pB);
-    pp = __builtin_fma(R2, pp, pC);
-    const double q = __builtin_fma(pp, R, tl[j]);
-    const double thj = th[j];
-    const double res = ldexp(__builtin_fma(thj, q, thj), k16 >> 4);
+    const double res = gs_exp_core(inr ? x : 0.0, th, tl);
     return far ? 0.0 : res;
 }
 
-// base value with the exp argument's class reported: far = the exponential is exactly zero
+// base value of a family at the squared scaled distance s, through the exp `ex`.  FAMILY: int for a run-time family,
+// std::integral_constant<int, GSUM_...> for a compile-time one (its tests fold away; one chain of tests and one sqrt either way)
+template <class FAMILY, class EXP>
+__device__ __forceinline__ double gs_base_value_e(FAMILY family, double s, EXP ex) {
+#pragma clang fp contract(off)
+    if (family == GSUM_RBF) return ex(-0.5 * s);
+    const double dist = sqrt(s);
+    if (family == GSUM_MATERN52) {
+        const double t = dist * 2.23606797749979;      // math.sqrt(5)
+        return (1.0 + t + (t * t) / 3.0) * ex(-t);
+    }
+    if (family == GSUM_MATERN32) {
+        const double t = dist * 1.7320508075688772;    // math.sqrt(3)
+        return (1.0 + t) * ex(-t);
+    }
+    return ex(-dist);
+}
+
+// run-time family, __constant__ tables (the gradient and tree paths)
+__device__ __forceinline__ double gs_base_value(int family, double s) {
+    return gs_base_value_e(family, s, [](double x) __attribute__((always_inline)) { return gs_exp_np(x); });
+}
+
+// ---- second version of the kernel build (round 2) ---------------------------------------------------------------
+// The first version was bound by instruction issue, not by HBM: a runtime switch over the kernel family and a runtime
+// loop over the input dimensions inside the per-entry loop, the 2^(j/16) table read through divergent global loads from
+// constant memory, a 64-bit float -> integer conversion, and diagonal / padding tests on every entry: ~90 VALU
+// instructions per entry, 89 us for the 34 M entries of the n = 8192 lower triangle (3.1 TB/s of stores).  Here the
+// family and the one-dimensional case are template parameters, the table lives in LDS, the exponent goes through
+// v_cvt_i32_f64, tiles that touch neither the diagonal nor the padding skip every test, and a workgroup takes 32 x 128
+// entries (8320 tiles at n = 8192: 4 rounds of the 2048 resident workgroups instead of 1.02 with a one-tile tail).
+// Same arithmetic, operation for operation (array_equal to scikit-learn is asserted on the device for every family).
+
+// compile-time family, tables through pointers (LDS in the build kernels)
+template <int FAM>
+__device__ __forceinline__ double gs_base_value_t(double s, const double* th, const double* tl) {
+    return gs_base_value_e(std::integral_constant<int, FAM>(), s,
+                           [=](double x) __attribute__((always_inline)) { return gs_exp_np_t(x, th, tl); });
+}
+
+// the branch-free form, with the exp argument's class reported (slow: recompute with gs_base_value_t)
 template <int FAM>
 __device__ __forceinline__ double gs_base_value_nb(double s, const double* th, const double* tl, bool& slow) {
-#pragma clang fp contract(off)
-    if (FAM == GSUM_RBF) return gs_exp_np_nobranch(-0.5 * s, th, tl, slow);
-    const double dist = sqrt(s);
-    if (FAM == GSUM_MATERN52) {
-        const double t = dist * 2.23606797749979;
-        return (1.0 + t + (t * t) / 3.0) * gs_exp_np_nobranch(-t, th, tl, slow);
-    }
-    if (FAM == GSUM_MATERN32) {
-        const double t = dist * 1.7320508075688772;
-        return (1.0 + t) * gs_exp_np_nobranch(-t, th, tl, slow);
-    }
-    return gs_exp_np_nobranch(-dist, th, tl, slow);
+    return gs_base_value_e(std::integral_constant<int, FAM>(), s,
+                           [=, &slow](double x) __attribute__((always_inline)) { return gs_exp_np_nobranch(x, th, tl, slow); });
 }
 
 // is the exponential of this squared scaled distance exactly zero?  (the argument of exp is -0.5 s, -sqrt(5 s), ...)
@@ -188,26 +145,90 @@ __device__ __forceinline__ bool gs_base_is_zero(double s) {
     return s > 555500.0;                                          // sqrt(s) > 745.3
 }
 
-// run-time family, exp tables in LDS (the fused one-workgroup kernels: the family is uniform over the workgroup, and a table
-// in LDS costs an LDS read per entry where the __constant__ one of gs_exp_np costs a vector load from memory)
-__device__ __forceinline__ double gs_base_value_f(int family, double s, const double* th, const double* tl) {
-    if (family == GSUM_RBF) return gs_base_value_t<GSUM_RBF>(s, th, tl);
-    if (family == GSUM_MATERN52) return gs_base_value_t<GSUM_MATERN52>(s, th, tl);
-    if (family == GSUM_MATERN32) return gs_base_value_t<GSUM_MATERN32>(s, th, tl);
-    return gs_base_value_t<GSUM_MATERN12>(s, th, tl);
+// ---- the tile body shared by k_build2 (32 x 128 tiles) and gs_build_tile128 (128 x 128 tiles inside the fused kernels) ----
+// ui / uj: the scaled coordinates of the tile's rows / columns in LDS; th / tl: the exp tables in LDS.  A lane owns two
+// adjacent columns and takes two rows per pass; which two rows, the CROSS rule, diag0 and the store are the caller's.
+// The ten lines that load the lane's two column points stay in both callers: moved into a function (pointer, array-reference
+// and by-value forms were compiled) they changed the scalar-register count of every k_build2<*, *, false> and the spills of
+// k_lml_medium, and this code has to compile to what it was.
+
+// squared scaled distances of tile row rr to the lane's two columns
+template <bool D1>
+__device__ __forceinline__ void gs_row_sqdist(const double* ui, int rr, int d, const double* vj0, const double* vj1, double* s) {
+#pragma clang fp contract(off)
+    if (D1) {
+        const double xi = ui[rr];
+        const double e0 = xi - vj0[0], e1 = xi - vj1[0];
+        s[0] = e0 * e0;
+        s[1] = e1 * e1;
+    } else {
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int dd = 0; dd < GSUM_MAX_D; ++dd) {
+            if (dd < d) {
+                const double xi = ui[rr * d + dd];
+                const double e0 = xi - vj0[dd], e1 = xi - vj1[dd];
+                s0 = s0 + e0 * e0;
+                s1 = s1 + e1 * e1;
+            }
+        }
+        s[0] = s0;
+        s[1] = s1;
+    }
 }
 
-// One 128 x 128 tile of the kernel matrix for the fused one-workgroup kernels (256 threads; ui / uj: the scaled coordinates
-// of the tile's rows / columns in LDS; th / tl: the exp tables in LDS): k_build2's per-entry arithmetic and its short cuts
-// -- family and the one-dimensional case as template parameters, tiles that touch neither the diagonal nor the padding
-// without per-entry tests, two rows per pass -- instead of the round-1 loop (runtime family switch and dimension loop,
-// diagonal and padding tests on every entry: ~90 VALU instructions per entry, 17-21 % of k_lml_medium at n = 512 ... 1024).
+// a row pair of a plain tile (no entry needs a diagonal or padding rule): value = amplitude * base + additive.  Both ballots
+// are over the wave's 2 x 128 entries and must be reached by the whole wave.
+template <int FAM>
+__device__ __forceinline__ void gs_plain_pair(const double (&s)[2][2], double amp, double addc, const double* th, const double* tl,
+                                              double (&v)[2][2]) {
+#pragma clang fp contract(off)
+    // wave-uniform short cut: every exponential of these 2 x 128 entries is exactly zero
+    const bool nz = !(gs_base_is_zero<FAM>(s[0][0]) && gs_base_is_zero<FAM>(s[0][1]) && gs_base_is_zero<FAM>(s[1][0]) &&
+                      gs_base_is_zero<FAM>(s[1][1]));
+    if (__builtin_amdgcn_ballot_w64(nz) == 0) {
+        const double z = amp * 0.0 + addc;
+        v[0][0] = v[0][1] = v[1][0] = v[1][1] = z;
+        return;
+    }
+    bool slow[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) v[h][c] = amp * gs_base_value_nb<FAM>(s[h][c], th, tl, slow[h][c]) + addc;
+    if (__builtin_amdgcn_ballot_w64(slow[0][0] || slow[0][1] || slow[1][0] || slow[1][1]) != 0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                if (slow[h][c]) v[h][c] = amp * gs_base_value_t<FAM>(s[h][c], th, tl) + addc;
+    }
+}
+
+// entry (gi, gj) of the one-argument form on a tile that touches the diagonal or the padding
+template <int FAM>
+__device__ __forceinline__ double gs_edge_value(double s, int gi, int gj, int n, const gsum_kernel_desc& desc, double diag_add,
+                                                const double* th, const double* tl) {
+#pragma clang fp contract(off)
+    if (gi >= n || gj >= n) return gi == gj ? 1.0 : 0.0;           // identity padding up to a multiple of 128
+    const bool dg = gi == gj;
+    const double b = dg ? 1.0 : gs_base_value_t<FAM>(s, th, tl);   // np.fill_diagonal(K, 1)
+    double val = desc.amplitude * b;
+    if (dg) val = val + desc.white_noise;
+    val = val + desc.additive_const;
+    if (dg) val = val + diag_add;
+    return val;
+}
+
+// One 128 x 128 tile of the kernel matrix for the fused one-workgroup kernels (256 threads): k_build2's per-entry arithmetic
+// and its short cuts -- family and the one-dimensional case as template parameters, tiles that touch neither the diagonal nor
+// the padding without per-entry tests, two rows per pass -- instead of the round-1 loop (runtime family switch and dimension
+// loop, diagonal and padding tests on every entry: ~90 VALU instructions per entry, 17-21 % of k_lml_medium at n = 512 ... 1024).
 // Wave w takes rows w, w + 4, ... ; each lane two adjacent columns.  The diagonal's values also go to diag0.
 template <int FAM, bool D1>
 __device__ __forceinline__ void gs_build_tile128(double* A, int64_t ld, const double* ui, const double* uj, const double* th,
                                                  const double* tl, int bi, int bj, int n, int d, const gsum_kernel_desc& desc,
                                                  double diag_add, double* diag0, int w, int lane) {
-#pragma clang fp contract(off)
     double vj0[D1 ? 1 : GSUM_MAX_D], vj1[D1 ? 1 : GSUM_MAX_D];
     if (D1) {
         vj0[0] = uj[2 * lane];
@@ -224,70 +245,19 @@ __device__ __forceinline__ void gs_build_tile128(double* A, int64_t ld, const do
     const double amp = desc.amplitude, addc = desc.additive_const;
 #pragma unroll 1
     for (int rp = w; rp < 128; rp += 8) {
-        double s[2][2];
+        double s[2][2], v[2][2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int rr = rp + 4 * h;
-            if (D1) {
-                const double xi = ui[rr];
-                const double e0 = xi - vj0[0], e1 = xi - vj1[0];
-                s[h][0] = e0 * e0;
-                s[h][1] = e1 * e1;
-            } else {
-                double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                for (int dd = 0; dd < GSUM_MAX_D; ++dd) {
-                    if (dd < d) {
-                        const double xi = ui[rr * d + dd];
-                        const double e0 = xi - vj0[dd], e1 = xi - vj1[dd];
-                        s0 = s0 + e0 * e0;
-                        s1 = s1 + e1 * e1;
-                    }
-                }
-                s[h][0] = s0;
-                s[h][1] = s1;
-            }
-        }
-        double v[2][2];
+        for (int h = 0; h < 2; ++h) gs_row_sqdist<D1>(ui, rp + 4 * h, d, vj0, vj1, s[h]);
         if (plain) {
-            const bool nz = !(gs_base_is_zero<FAM>(s[0][0]) && gs_base_is_zero<FAM>(s[0][1]) && gs_base_is_zero<FAM>(s[1][0]) &&
-                              gs_base_is_zero<FAM>(s[1][1]));
-            if (__builtin_amdgcn_ballot_w64(nz) == 0) {
-                const double z = amp * 0.0 + addc;
-                v[0][0] = v[0][1] = v[1][0] = v[1][1] = z;
-            } else {
-                bool slow[2][2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) v[h][c] = amp * gs_base_value_nb<FAM>(s[h][c], th, tl, slow[h][c]) + addc;
-                if (__builtin_amdgcn_ballot_w64(slow[0][0] || slow[0][1] || slow[1][0] || slow[1][1]) != 0) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int c = 0; c < 2; ++c)
-                            if (slow[h][c]) v[h][c] = amp * gs_base_value_t<FAM>(s[h][c], th, tl) + addc;
-                }
-            }
+            gs_plain_pair<FAM>(s, amp, addc, th, tl, v);
         } else {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int gi = r0 + rp + 4 * h, gj = gj0 + c;
-                    double val;
-                    if (gi >= n || gj >= n) {
-                        val = (gi == gj) ? 1.0 : 0.0;                 // identity padding up to a multiple of 128
-                    } else {
-                        const bool dg = gi == gj;
-                        const double b = dg ? 1.0 : gs_base_value_t<FAM>(s[h][c], th, tl);   // np.fill_diagonal(K, 1)
-                        val = amp * b;
-                        if (dg) val = val + desc.white_noise;
-                        val = val + addc;
-                        if (dg) val = val + diag_add;
-                    }
-                    if (gi == gj) diag0[gi] = val;
-                    v[h][c] = val;
+                    v[h][c] = gs_edge_value<FAM>(s[h][c], gi, gj, n, desc, diag_add, th, tl);
+                    if (gi == gj) diag0[gi] = v[h][c];
                 }
         }
 #pragma unroll
@@ -313,18 +283,9 @@ __device__ __forceinline__ void gs_build_tile128_any(double* A, int64_t ld, cons
 }
 
 #define GS_B2_ROWS 32
-// One 32 x 128 tile per 256-thread workgroup: wave w takes rows 8 w .. 8 w + 7, two at a time; each lane owns two adjacent
-// columns (one 16-B store per row, 1 KiB per wave-instruction).  Grid: CROSS or tri == 0: (prow / 32 rounded up) x (pcol /
-// 128 rounded up) tiles, row-slice fastest; tri != 0: the 128-column tiles on or below the diagonal, four row slices each.
-template <bool CROSS, int FAM, bool D1>
-__global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const double* X, const double* Y, int n, int m,
-                                                 int prow, int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri) {
+// the tile of this workgroup of k_build2 / k_build_tree: 32-row slice bi, 128-column tile bj (the grids are described below)
+__device__ __forceinline__ void gs_b2_tile(int prow, int tri, int& bi, int& bj) {
 #pragma clang fp contract(off)
-    __shared__ double ui[GS_B2_ROWS * GSUM_MAX_D];
-    __shared__ double uj[128 * GSUM_MAX_D];
-    __shared__ double tab[32];
-    const int t = threadIdx.x;
-    int bi, bj;                                        // 32-row slice index, 128-column tile index
     if (tri) {
         const int bid = blockIdx.x >> 2;
         int b128 = (int)((sqrt(8.0 * (double)bid + 1.0) - 1.0) * 0.5);
@@ -337,6 +298,21 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
         bi = blockIdx.x % tr;
         bj = blockIdx.x / tr;
     }
+}
+
+// One 32 x 128 tile per 256-thread workgroup: wave w takes rows 8 w .. 8 w + 7, two at a time; each lane owns two adjacent
+// columns (one 16-B store per row, 1 KiB per wave-instruction).  Grid: CROSS or tri == 0: (prow / 32 rounded up) x (pcol /
+// 128 rounded up) tiles, row-slice fastest; tri != 0: the 128-column tiles on or below the diagonal, four row slices each.
+template <bool CROSS, int FAM, bool D1>
+__global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const double* X, const double* Y, int n, int m,
+                                                 int prow, int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri) {
+#pragma clang fp contract(off)
+    __shared__ double ui[GS_B2_ROWS * GSUM_MAX_D];
+    __shared__ double uj[128 * GSUM_MAX_D];
+    __shared__ double tab[32];
+    const int t = threadIdx.x;
+    int bi, bj;
+    gs_b2_tile(prow, tri, bi, bj);
     const double* Yp = CROSS ? Y : X;
     const int ny = CROSS ? m : n;
     const int r0 = bi * GS_B2_ROWS, c0 = bj * 128;
@@ -375,72 +351,19 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
     const double amp = desc.amplitude, addc = desc.additive_const;
 #pragma unroll 1
     for (int rp = 0; rp < 8; rp += 2) {
-        double s[2][2];
+        double s[2][2], v[2][2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int rr = 8 * w + rp + h;
-            if (D1) {
-                const double xi = ui[rr];
-                const double e0 = xi - vj0[0], e1 = xi - vj1[0];
-                s[h][0] = e0 * e0;
-                s[h][1] = e1 * e1;
-            } else {
-                double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                for (int dd = 0; dd < GSUM_MAX_D; ++dd) {
-                    if (dd < d) {
-                        const double xi = ui[rr * d + dd];
-                        const double e0 = xi - vj0[dd], e1 = xi - vj1[dd];
-                        s0 = s0 + e0 * e0;
-                        s1 = s1 + e1 * e1;
-                    }
-                }
-                s[h][0] = s0;
-                s[h][1] = s1;
-            }
-        }
-        double v[2][2];
+        for (int h = 0; h < 2; ++h) gs_row_sqdist<D1>(ui, 8 * w + rp + h, d, vj0, vj1, s[h]);
         if (plain) {
-            // wave-uniform short cut: every exponential of these 2 x 128 entries is exactly zero
-            const bool nz = !(gs_base_is_zero<FAM>(s[0][0]) && gs_base_is_zero<FAM>(s[0][1]) && gs_base_is_zero<FAM>(s[1][0]) &&
-                              gs_base_is_zero<FAM>(s[1][1]));
-            if (__builtin_amdgcn_ballot_w64(nz) == 0) {
-                const double z = amp * 0.0 + addc;
-                v[0][0] = v[0][1] = v[1][0] = v[1][1] = z;
-            } else {
-                bool slow[2][2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) v[h][c] = amp * gs_base_value_nb<FAM>(s[h][c], th, tl, slow[h][c]) + addc;
-                if (__builtin_amdgcn_ballot_w64(slow[0][0] || slow[0][1] || slow[1][0] || slow[1][1]) != 0) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                        for (int c = 0; c < 2; ++c)
-                            if (slow[h][c]) v[h][c] = amp * gs_base_value_t<FAM>(s[h][c], th, tl) + addc;
-                }
-            }
+            gs_plain_pair<FAM>(s, amp, addc, th, tl, v);
         } else {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const int gi = r0 + 8 * w + rp + h, gj = gj0 + c;
-                    double val;
-                    if (CROSS) {
-                        val = (gi < n && gj < m) ? amp * gs_base_value_t<FAM>(s[h][c], th, tl) + addc : 0.0;
-                    } else if (gi >= n || gj >= n) {
-                        val = (gi == gj) ? 1.0 : 0.0;                 // identity padding up to a multiple of 128
-                    } else {
-                        const bool dg = gi == gj;
-                        const double b = dg ? 1.0 : gs_base_value_t<FAM>(s[h][c], th, tl);   // np.fill_diagonal(K, 1)
-                        val = amp * b;
-                        if (dg) val = val + desc.white_noise;
-                        val = val + addc;
-                        if (dg) val = val + diag_add;
-                    }
-                    v[h][c] = val;
+                    if (CROSS) v[h][c] = (gi < n && gj < m) ? amp * gs_base_value_t<FAM>(s[h][c], th, tl) + addc : 0.0;
+                    else v[h][c] = gs_edge_value<FAM>(s[h][c], gi, gj, n, desc, diag_add, th, tl);
                 }
         }
 #pragma unroll
@@ -464,6 +387,21 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
 // The same walk with dual numbers gives d kernel / d log(parameter) for the gradient path (sklearn's K_gradient formulas per leaf:
 // RBF :1567-1577, Matern :1740-1771, RationalQuadratic :1893-1901; product and sum rules for the operators).
 #define GS_TREE_STACK 8
+
+// d / d log length_scale of an RBF / Matern 5/2, 3/2, 1/2 leaf (sklearn's K_gradient: RBF :1567-1577, Matern :1740-1771) for the flattened
+// gradient (gs_kernel_grad) and the tree walk (gs_leaf_eval).  s = sum_m D_m, D_m = ((x_im - x_jm) / l_m)^2, formed by the caller in its own
+// way; dm = s for an isotropic length scale, D_dim for one dimension's; v = the leaf's value at s (read by RBF and Matern 1/2 only).
+__device__ __forceinline__ double gs_leaf_dlog_ls(int family, double s, double dm, double v) {
+#pragma clang fp contract(off)
+    if (family == GSUM_RBF) return v * dm;
+    if (family == GSUM_MATERN52) {
+        const double tmp = sqrt(5.0 * s);
+        return 5.0 / 3.0 * dm * (tmp + 1.0) * gs_exp_np(-tmp);
+    }
+    if (family == GSUM_MATERN32) return 3.0 * dm * gs_exp_np(-sqrt(3.0 * s));
+    const double den = sqrt(s);
+    return den != 0.0 ? v * (dm / den) : 0.0;
+}
 
 // want: 0 value only, 1 d / d log length_scale (isotropic), 2 d / d log length_scale[dim], 3 d / d log alpha
 // cross: the TWO-argument form kernel(X, Y) (it differs from the one-argument form off the diagonal only where scikit-learn orders the arithmetic
@@ -529,20 +467,7 @@ __device__ __forceinline__ void gs_leaf_eval(const gsum_kernel_leaf& lf, const d
         return;
     }
     v = gs_base_value(lf.family, s);
-    if (want == 1 || want == 2) {
-        const double dm = want == 1 ? s : dsel;
-        if (lf.family == GSUM_RBF) {
-            dv = v * dm;
-        } else if (lf.family == GSUM_MATERN52) {
-            const double tmp = sqrt(5.0 * s);
-            dv = 5.0 / 3.0 * dm * (tmp + 1.0) * gs_exp_np(-tmp);
-        } else if (lf.family == GSUM_MATERN32) {
-            dv = 3.0 * dm * gs_exp_np(-sqrt(3.0 * s));
-        } else {
-            const double den = sqrt(s);
-            dv = den != 0.0 ? v * (dm / den) : 0.0;
-        }
-    }
+    if (want == 1 || want == 2) dv = gs_leaf_dlog_ls(lf.family, s, want == 1 ? s : dsel, v);
 }
 
 // value of the tree at (xi, xj); diag: the entry is on the diagonal of the ONE-argument form (leaves exactly 1, WhiteKernel on).
@@ -597,10 +522,20 @@ __device__ __forceinline__ double gs_tree_eval(const gsum_kernel_desc& t, const 
     return sv[0];
 }
 
+// entry (gi, gj) of the one-argument form of a tree's matrix (k_build_tree and gs_build_tile128_tree): identity padding beyond n, the value
+// through gs_tree_eval on the points themselves (a tree's leaves divide by their own length scales), diag_add on the diagonal
+__device__ __forceinline__ double gs_tree_entry(const gsum_kernel_desc& desc, const double* xi, const double* xj, int d, int gi, int gj, int n,
+                                                double diag_add) {
+#pragma clang fp contract(off)
+    if (gi >= n || gj >= n) return gi == gj ? 1.0 : 0.0;           // identity padding
+    double v = gs_tree_eval(desc, xi, xj, d, gi == gj, nullptr, nullptr);
+    if (gi == gj) v = v + diag_add;
+    return v;
+}
+
 // One 128 x 128 tile of a tree's matrix inside the one-workgroup-per-evaluation kernels (k_lml_small / k_lml_medium): the geometry
-// and the diagonal / padding rules of gs_build_tile128's general branch (wave w takes rows w, w + 4, ...; a lane two adjacent
-// columns; identity padding beyond n; the diagonal's values also to diag0), the values through gs_tree_eval on the points themselves
-// (a tree's leaves divide by their own length scales) -- so the matrix equals k_build_tree's bit for bit.  `desc` stays where it
+// of gs_build_tile128 (wave w takes rows w, w + 4, ...; a lane two adjacent columns; the diagonal's values also to diag0), the
+// values through gs_tree_entry -- so the matrix equals k_build_tree's bit for bit.  `desc` stays where it
 // is (global memory, uniform address: scalar loads), the program is walked with dynamic indices.
 __device__ __forceinline__ void gs_build_tile128_tree(double* A, int64_t ld, const double* X, int bi, int bj, int n, int d,
                                                       const gsum_kernel_desc& desc, double diag_add, double* diag0, int w, int lane) {
@@ -621,12 +556,7 @@ __device__ __forceinline__ void gs_build_tile128_tree(double* A, int64_t ld, con
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int gj = gj0 + c;
-            if (gi >= n || gj >= n) {
-                v[c] = gi == gj ? 1.0 : 0.0;                       // identity padding
-            } else {
-                v[c] = gs_tree_eval(desc, xi, xj[c], d, gi == gj, nullptr, nullptr);
-                if (gi == gj) v[c] = v[c] + diag_add;
-            }
+            v[c] = gs_tree_entry(desc, xi, xj[c], d, gi, gj, n, diag_add);
             if (gi == gj) diag0[gi] = v[c];
         }
         const gs_d2 o = {v[0], v[1]};
@@ -641,18 +571,7 @@ __global__ __launch_bounds__(256) void k_build_tree(double* out, int64_t ldo, co
 #pragma clang fp contract(off)
     const int t = threadIdx.x;
     int bi, bj;
-    if (tri) {
-        const int bid = blockIdx.x >> 2;
-        int b128 = (int)((sqrt(8.0 * (double)bid + 1.0) - 1.0) * 0.5);
-        while ((int64_t)(b128 + 1) * (b128 + 2) / 2 <= bid) ++b128;
-        while ((int64_t)b128 * (b128 + 1) / 2 > bid) --b128;
-        bj = bid - (int)((int64_t)b128 * (b128 + 1) / 2);
-        bi = 4 * b128 + (blockIdx.x & 3);
-    } else {
-        const int tr = (prow + GS_B2_ROWS - 1) / GS_B2_ROWS;
-        bi = blockIdx.x % tr;
-        bj = blockIdx.x / tr;
-    }
+    gs_b2_tile(prow, tri, bi, bj);
     const double* Yp = CROSS ? Y : X;
     const int ny = CROSS ? m : n;
     const int lane = t & 63, w = t >> 6;
@@ -673,14 +592,8 @@ __global__ __launch_bounds__(256) void k_build_tree(double* out, int64_t ldo, co
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int gj = gj0 + c;
-            if (CROSS) {
-                v[c] = (gi < n && gj < m) ? gs_tree_eval(desc, xi, xj[c], d, false, nullptr, nullptr, true) : 0.0;
-            } else if (gi >= n || gj >= n) {
-                v[c] = gi == gj ? 1.0 : 0.0;                       // identity padding
-            } else {
-                v[c] = gs_tree_eval(desc, xi, xj[c], d, gi == gj, nullptr, nullptr);
-                if (gi == gj) v[c] = v[c] + diag_add;
-            }
+            if (CROSS) v[c] = (gi < n && gj < m) ? gs_tree_eval(desc, xi, xj[c], d, false, nullptr, nullptr, true) : 0.0;
+            else v[c] = gs_tree_entry(desc, xi, xj[c], d, gi, gj, n, diag_add);
         }
         const gs_d2 o = {v[0], v[1]};
         *reinterpret_cast<gs_d2*>(out + (int64_t)gi * ldo + gj0) = o;

@@ -22,19 +22,9 @@ __device__ __forceinline__ double gs_kernel_grad(const gsum_kernel_desc& desc, c
         default: break;
     }
     if (diag) return 0.0;
-    double g;
-    if (desc.family == GSUM_RBF) {
-        g = gs_base_value(GSUM_RBF, s) * dm;
-    } else if (desc.family == GSUM_MATERN52) {
-        const double tmp = sqrt(5.0 * s);
-        g = 5.0 / 3.0 * dm * (tmp + 1.0) * gs_exp_np(-tmp);
-    } else if (desc.family == GSUM_MATERN32) {
-        g = 3.0 * dm * gs_exp_np(-sqrt(3.0 * s));
-    } else {
-        const double den = sqrt(s);
-        g = den != 0.0 ? gs_base_value(GSUM_MATERN12, s) * (dm / den) : 0.0;
-    }
-    return desc.amplitude * g;
+    const int f = desc.family;
+    const double v = (f == GSUM_MATERN52 || f == GSUM_MATERN32) ? 0.0 : gs_base_value(f, s);   // those two derivatives do not read the value
+    return desc.amplitude * gs_leaf_dlog_ls(f, s, dm, v);
 }
 
 // One wave per row i of dR_p (grid.y = p): Q_p[i][c] = sum_j dR_p,ij V[j][c] (V^T given as 16 rows: coalesced loads)

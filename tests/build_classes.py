@@ -4,7 +4,7 @@ Every entry of a kernel matrix takes the exponential of an argument x (gsum_amd/
 s = sum_m (u_im - u_jm)^2 summed in feature order; RBF x = -s / 2; Matern d = sqrt(s), t = d sqrt(3) or d sqrt(5), x = -t; Matern 1/2 x = -d)
 and x falls into one of three classes, which the build treats differently:
 
-    IN_RANGE   |x| < 707.7 (0x1.61da04cbafe44p+9)     numpy's table algorithm restated (gs_exp_np, gs_exp_np_t, gs_exp_np_nobranch)
+    IN_RANGE   |x| < 707.7 (0x1.61da04cbafe44p+9)     numpy's table algorithm restated (gs_exp_core, behind gs_exp_np, gs_exp_np_t, gs_exp_np_nobranch)
     BAND       -745.2 <= x <= -707.7                  the result is subnormal (or rounds to zero: exp(x) = 0 from x < -745.1332): the device
                                                       library's exp; in full off-diagonal ("plain") tiles after a wave-wide ballot
     FAR        x < -745.2                             exactly 0.0; a two-row x 128-column group that is far throughout skips the arithmetic
@@ -35,7 +35,7 @@ import numpy as np
 LD = np.longdouble
 IN_RANGE, BAND, FAR = 0, 1, 2
 CLASS_NAMES = ("in range", "band", "far")
-IN_RANGE_LIMIT = float.fromhex("0x1.61da04cbafe44p+9")       # 707.7...: gs_exp_np's fast-path limit
+IN_RANGE_LIMIT = float.fromhex("0x1.61da04cbafe44p+9")       # 707.7...: GS_EXP_INRANGE, the table algorithm's limit
 FAR_LIMIT = -745.2                                          # gs_exp_np_nobranch's far threshold
 SUBNORMAL = 5e-324
 ULPS = 4

@@ -20,7 +20,9 @@ def test_class_limits_are_the_build_kernels_own():
     import os
     from conftest import ROOT
     src = open(os.path.join(ROOT, "gsum_amd", "csrc", "kernels", "build.hip.h")).read()
-    assert "const bool far = x < -745.2;" in src and "const bool inr = fabs(x) < 0x1.61da04cbafe44p+9;" in src
+    assert "const bool far = x < -745.2;" in src and "const bool inr = fabs(x) < GS_EXP_INRANGE;" in src
+    assert "if (!(fabs(x) < GS_EXP_INRANGE)) return exp(x);" in src                              # the branching form: the same limit
+    assert src.count("#define GS_EXP_INRANGE") == 1 and "#define GS_EXP_INRANGE 0x1.61da04cbafe44p+9 " in src
     assert bc.FAR_LIMIT == -745.2 and bc.IN_RANGE_LIMIT == float.fromhex("0x1.61da04cbafe44p+9")
     assert np.exp(np.nextafter(bc.FAR_LIMIT, 0.0)) == 0.0 and np.exp(bc.FAR_LIMIT) == 0.0        # far: exactly zero, with room
     assert np.exp(-bc.IN_RANGE_LIMIT) > 1.99 * np.finfo(float).tiny                               # in range: normal (two times the smallest)

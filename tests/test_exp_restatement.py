@@ -2,7 +2,8 @@
 routine numpy's float64 exp dispatches to on AVX512 hosts (Intel SVML __svml_exp8_ha), because that
 routine is not correctly rounded and a single differing ulp in one kernel value moves the uniform-grid
 log-likelihood by 6e-10.  This CPU test pins the restatement: a Python model of
-gs_exp_np (gsum_amd/csrc/kernels/build.hip.h) with exactly rounded FMAs must equal np.exp bit for bit.
+gs_exp_core (gsum_amd/csrc/kernels/build.hip.h: the one body behind gs_exp_np, gs_exp_np_t and gs_exp_np_nobranch) with exactly
+rounded FMAs must equal np.exp bit for bit, and every constant of it is written once in the device sources.
 The same check runs against the device in tests/test_gpu_parity.py::test_kernel_matrix_matches_sklearn."""
 import math
 import re
@@ -14,17 +15,23 @@ import pytest
 from conftest import ROOT
 
 H = float.fromhex
+HEX =r"-?0x[0-9a-f.]+p[+-]\d+"
+
+
+def _core_source():
+    """The range limit and gs_exp_core: the one place the restatement's constants are written."""
+    src = open(f"{ROOT}/gsum_amd/csrc/kernels/build.hip.h").read()
+    return src, src[src.index("#define GS_EXP_INRANGE"):src.index("double gs_exp_np_t(")]
 
 
 def _device_constants():
     """Read the tables / coefficients straight from the HIP source, so the test pins what ships."""
-    src = open(f"{ROOT}/gsum_amd/csrc/kernels/build.hip.h").read()
+    src, body = _core_source()
+    assert "double gs_exp_core(" in body
     th = re.search(r"gs_exp_th\[16\] = \{(.*?)\};", src, re.S).group(1)
     tl = re.search(r"gs_exp_tl\[16\] = \{(.*?)\};", src, re.S).group(1)
-    body = src[src.index("double gs_exp_np(double x)"):src.index("double gs_base_value")]
-    hexes = re.findall(r"-?0x[0-9a-f.]+p[+-]\d+", body)
-    return [H(v) for v in re.findall(r"-?0x[0-9a-f.]+p[+-]\d+", th)], \
-           [H(v) for v in re.findall(r"-?0x[0-9a-f.]+p[+-]\d+", tl)], [H(v) for v in hexes]
+    hexes = re.findall(HEX, body)
+    return [H(v) for v in re.findall(HEX, th)], [H(v) for v in re.findall(HEX, tl)], [H(v) for v in hexes]
 
 
 def fma(a, b, c):
@@ -63,6 +70,19 @@ def test_constants_parse():
     assert len(TH) == 16 and len(TL) == 16 and len(c) >= 11
     assert TH[0] == 1.0 and TH[8] == math.sqrt(2.0) and TL[0] == 0.0
     assert c[0] == H("0x1.61da04cbafe44p+9") and c[1] == H("0x1.71547652b82fep+0")
+
+
+def test_each_constant_is_written_once():
+    """One definition: the range limit, the four reduction constants and the six polynomial coefficients each occur exactly once
+    in the device sources, so the model above pins the exp of every path (kernel build, fused likelihood, gradient, trees)."""
+    import glob
+    literals = re.findall(HEX, _core_source()[1])
+    assert len(literals) == 11 and len(set(literals)) == 11
+    files = [f for f in glob.glob(f"{ROOT}/gsum_amd/csrc/**/*", recursive=True) if f.endswith((".h", ".hip", ".hpp", ".cpp"))]
+    assert f"{ROOT}/gsum_amd/csrc/kernels/build.hip.h" in files
+    text = "".join(open(f).read() for f in files).lower()
+    counts = {v: text.count(v.lstrip("-")) for v in literals}
+    assert all(n == 1 for n in counts.values()), counts
 
 
 @pytest.mark.skipif(not _numpy_uses_svml(), reason="host numpy does not dispatch exp to SVML (no AVX512_SKX)")

@@ -162,7 +162,7 @@ def _both_paths(ctx, X, Z, descs, nugget):
 @pytest.mark.parametrize("design", bc.DESIGNS, ids=bc.DESIGN_IDS)
 def test_medium_fused_path_and_truth(ctx, design):
     """Steps 2 and 3.  The design's kernel and two neighbours in theta (the band moves by a few diagonals) through k_lml_medium --
-    gs_build_tile128's own copy of the two ballots, 128 x 128 tiles with row pairs (r, r + 4) -- and through the general path: G, sum log
+    gs_build_tile128: the two ballots of gs_plain_pair on 128 x 128 tiles with row pairs (r, r + 4) -- and through the general path: G, sum log
     L_ii and info bit-identical, as test_medium_fused_path_matches_general_path asserts on inputs without band or far entries.  One design
     per family then goes against the long-double Cholesky of scikit-learn's matrix (tests/grad_truth.py's): sum log L_ii within 1e-10
     relative, G within 1e-10 of |W|^T |W| entrywise (the magnitude of the terms an entry of G = W^T W sums; on its diagonal that is
