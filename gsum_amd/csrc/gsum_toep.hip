@@ -68,6 +68,13 @@ void with_size_class(int n, F&& f) {
         f(SizeClass<16, 3, true>{});
 }
 
+// E of n: the generator elements a k_schur thread holds and sums log L_jj over; beyond the size classes ceil(n / kThreads).
+int generator_elements(int64_t n) {
+    int E = (int)((n + gt::kThreads - 1) / gt::kThreads);
+    if (n <= gt::kMaxN) with_size_class((int)n, [&](auto k) { E = decltype(k)::E; });
+    return E;
+}
+
 // The Schur recursion of m first columns with the forward substitution of the ncols columns Z / ze beside it.  R: it also hands out
 // its reflection coefficients and rotations (steps, (m, n, 4)), which launch_levinson replays.
 template <bool R>
@@ -236,22 +243,24 @@ void solve_columns(const char* who, const SolvePhases& ph, gsum_toep* h, const d
 
 // ---- the panel route ----
 
-// Bytes one first column keeps on the device on the panel route: Y with its correction words, one panel, the generator state.
-size_t panel_bytes(int64_t n, int64_t ncols) {
-    size_t ne = 0;
-    with_size_class((int)n, [&](auto k) { ne = (size_t)gt::kThreads * decltype(k)::E; });
-    return (size_t)n * ncols * (sizeof(double) + sizeof(float)) + (size_t)n * gt::kPanelB * (sizeof(double) + sizeof(float)) + 4 * ne * sizeof(double);
+// What both routes keep on the device per first column, Y with its correction words and one panel: the bytes, and the buffers of
+// `step` first columns in flight.
+size_t shared_bytes(int64_t n, int64_t ncols) {
+    return (size_t)n * ncols * (sizeof(double) + sizeof(float)) + (size_t)n * gt::kPanelB * (sizeof(double) + sizeof(float));
 }
-
-// The buffers of `step` first columns in flight on the panel route.
-void reserve_panel(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
-    size_t ne = 0;
-    with_size_class((int)n, [&](auto k) { ne = (size_t)gt::kThreads * decltype(k)::E; });
+void reserve_shared(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
     h->Y.reserve((size_t)n * ncols * step);
     h->Zc.reserve((size_t)n * ncols * step);
     h->Ph.reserve((size_t)n * gt::kPanelB * step);
     h->Pl.reserve((size_t)n * gt::kPanelB * step);
-    h->Pst.reserve(4 * ne * step);
+}
+
+// The panel route adds the generator state, four planes of every thread's elements.
+size_t panel_state(int64_t n) { return (size_t)4 * gt::kThreads * generator_elements(n); }
+size_t panel_bytes(int64_t n, int64_t ncols) { return shared_bytes(n, ncols) + panel_state(n) * sizeof(double); }
+void reserve_panel(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
+    reserve_shared(h, n, ncols, step);
+    h->Pst.reserve(panel_state(n) * step);
 }
 
 // The scaled right-hand sides h->Z / h->ze into the working residuals h->Y of cnt first columns, their correction words zeroed.
@@ -301,19 +310,10 @@ void panel_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, d
 
 // ---- the blocked route ----
 
-// Bytes one first column keeps on the device on the blocked route: Y with its correction words, one panel, the two generator
-// states, the panel's coefficients and the diagonal of L.
-size_t blocked_bytes(int64_t n, int64_t ncols) {
-    return (size_t)n * ncols * (sizeof(double) + sizeof(float)) + (size_t)n * gt::kPanelB * (sizeof(double) + sizeof(float)) +
-           ((size_t)2 * 4 * n + 4 * gt::kPanelB + n) * sizeof(double);
-}
-
-// The buffers of `step` first columns in flight on the blocked route.
+// The blocked route adds the two generator states, the panel's coefficients and the diagonal of L.
+size_t blocked_bytes(int64_t n, int64_t ncols) { return shared_bytes(n, ncols) + ((size_t)2 * 4 * n + 4 * gt::kPanelB + n) * sizeof(double); }
 void reserve_blocked(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
-    h->Y.reserve((size_t)n * ncols * step);
-    h->Zc.reserve((size_t)n * ncols * step);
-    h->Ph.reserve((size_t)n * gt::kPanelB * step);
-    h->Pl.reserve((size_t)n * gt::kPanelB * step);
+    reserve_shared(h, n, ncols, step);
     h->Bst.reserve((size_t)2 * 4 * n * step);
     h->Bco.reserve((size_t)4 * gt::kPanelB * step);
     h->Bdg.reserve((size_t)n * step);
@@ -350,9 +350,7 @@ void blocked_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt,
         if (++panels % kBlockedSettle == 0) settle(h);
     }
     timed(h, kBTiles, [&] {
-        int E = (n + gt::kThreads - 1) / gt::kThreads;                         // beyond the size classes; within them k_schur's own
-        if (n <= gt::kMaxN) with_size_class(n, [&](auto k) { E = decltype(k)::E; });
-        gt::k_blocked_sld<<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->Bdg.p, n, E, sld, info);
+        gt::k_blocked_sld<<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->Bdg.p, n, generator_elements(n), sld, info);
         SL_LAUNCHED("k_blocked_sld");
     });
 }

@@ -25,12 +25,15 @@
 //   give tr(T^-1 dT_p), k_gs_first / k_gs_second alpha = T^-1 Z by Gohberg-Semencul, k_tprod / k_hdot alpha^T dT_p alpha.
 // The posterior pieces (the comments stand at the kernels): k_pred_sums gives the column sums of squares of
 //   L^-1 K and its products with L^-1 Z in double-double, k_pred_cov (L^-1 K)^T (L^-1 K) on the fp64 MFMA, k_invdiag diag(T^-1) from x.
-// The panel route (the comments stand at the kernels): k_schur_panel runs k_schur's step without residual columns
-//   and writes L in panels, k_panel_diag solves a panel's triangular block for every right-hand side, k_panel_update applies the
+// The panel route (the comments stand at the kernels): k_schur_panel runs k_schur's sweep without residual
+//   columns and writes L in panels, k_panel_diag solves a panel's triangular block for every right-hand side, k_panel_update applies the
 //   panel to the rows below on the fp64 MFMA, k_panel_load lays the scaled right-hand sides out row-major.
 // The blocked route (the comments stand at the kernels): k_schur_lead runs a panel's steps on the rows under the
 //   pivot and hands out their (rho, 1 / c), k_schur_tiles replays them on every row, tile by tile, from one state buffer in HBM
 //   into another, and writes the panel; k_blocked_init forms the state, k_blocked_sld sums the logarithms of the diagonal.
+// The step itself is written once, after the double-double functions: step_coeffs (rho, the failure test, 1 / c), rotate, the
+//   generator from t and its state in HBM, a column of L in the panel layout, the tree of sum log L_jj.  Every recursion kernel calls
+//   those, so the routes cannot differ in an expression; the order of their sweeps is their own, and the tests compare them.
 // Every value is written with ordinary vector stores; there are no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -101,6 +104,86 @@ __device__ __forceinline__ dd dd_rsqrt(dd a) {
     return quick_two_sum(x, x * r.h * 0.5);
 }
 
+// ---- the Schur step ---------------------------------------------------------------------------------------------------------------------
+// What every route of the recursion computes with, written here and nowhere else: the kernels below differ in where the generator
+// lives, how the shifted u reaches an element and which elements they keep, never in an expression.  Results come back by value:
+// with reference outputs the same rotate took k_schur<8, ..> from 0 to 8 / 16 bytes of scratch per lane and <16, ..> from 104 / 112 to
+// 200 / 208 (which also says why k_schur and k_schur_panel each keep their sweep loop).
+
+// (rho, 1 / c) of a step from its pivot pair pu = u[k], pv = v[k+1].  False where !(|rho| < 1), a NaN included: T is not positive
+// definite at order k + 2, the caller reports k + 2 and does not use ic.  The test reads rho.h alone.
+struct coeffs {
+    dd rho, ic;
+    bool ok;
+};
+__device__ __forceinline__ coeffs step_coeffs(dd pu, dd pv) {
+    const dd rho = dd_div(pv, pu);
+    const bool ok = fabs(rho.h) < 1.0;
+    return {rho, dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho))), ok};
+}
+struct uv {                                        // one element of the generator pair
+    dd u, v;
+};
+// The hyperbolic rotation of one element: us = u[i-1] (u shifted down by one), v = v[i], nrho = -rho.
+__device__ __forceinline__ uv rotate(dd us, dd v, dd nrho, dd ic) {
+    return {dd_mul(dd_add(us, dd_mul(nrho, v)), ic), dd_mul(dd_add(v, dd_mul(nrho, us)), ic)};
+}
+// The generator of T from its first column tt: 1 where t0 admits none, else rs = 1 / sqrt(t0), u[i] = rs t[i] (zero beyond n) and
+// v = u under the first row.
+__device__ __forceinline__ int t0_bad(double t0) { return (t0 > 0.0 && t0 < INFINITY) ? 0 : 1; }
+__device__ __forceinline__ dd t0_rsqrt(double t0) { return dd_rsqrt(dd{t0, 0.0}); }
+__device__ __forceinline__ uv generator_from_t(const double* __restrict__ tt, dd rs, int i, int n) {
+    const dd u = i < n ? dd_mul_d(rs, tt[i]) : dd{0.0, 0.0};
+    return {u, i > 0 ? u : dd{0.0, 0.0}};
+}
+// The generator state in HBM between launches: four planes of `stride` doubles, u.h, u.l, v.h, v.l.
+__device__ __forceinline__ uv state_load(const double* __restrict__ s, int64_t stride, int i) {
+    return {{s[i], s[stride + i]}, {s[2 * stride + i], s[3 * stride + i]}};
+}
+__device__ __forceinline__ void state_store(double* __restrict__ s, int64_t stride, int i, uv g) {
+    s[i] = g.u.h;
+    s[stride + i] = g.u.l;
+    s[2 * stride + i] = g.v.h;
+    s[3 * stride + i] = g.v.l;
+}
+// Row i of a column of L in the panel layout: the high word in pk, the low word as fp32 in qk.
+__device__ __forceinline__ void store_column(double* __restrict__ pk, float* __restrict__ qk, int i, dd u) {
+    pk[i] = u.h;
+    qk[i] = (float)u.l;
+}
+// sum log L_jj from the partial sum s of each of the kThreads threads (its consecutive entries in ascending order): the binary tree
+// over the threads through red[kThreads] in LDS; thread 0 writes the sum, NaN for a first column that failed.  Every thread calls it.
+__device__ __forceinline__ void sum_log_diag_tree(double* red, int tid, double s, int bad, double* __restrict__ sld) {
+    red[tid] = s;
+    __syncthreads();
+    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
+        if (tid < stride) red[tid] += red[tid + stride];
+        __syncthreads();
+    }
+    if (tid == 0) *sld = bad ? NAN : red[0];
+}
+
+// v of a thread's E generator elements in k_schur and k_schur_panel: in registers, or with VL (the largest size class) in LDS, where
+// slot points at the thread's own 16-byte slot of element 0 and element e lies kThreads slots further ([e][tid]).
+template <int E, bool VL>
+struct VStore {
+    double (*slot)[2];
+    double h[VL ? 1 : E], l[VL ? 1 : E];
+    __device__ __forceinline__ dd get(int e) const {
+        if constexpr (VL) return {slot[e * kThreads][0], slot[e * kThreads][1]};
+        else return {h[e], l[e]};
+    }
+    __device__ __forceinline__ void set(int e, dd x) {
+        if constexpr (VL) {
+            slot[e * kThreads][0] = x.h;
+            slot[e * kThreads][1] = x.l;
+        } else {
+            h[e] = x.h;
+            l[e] = x.l;
+        }
+    }
+};
+
 // ze[col] = ilogb(max_k |Z[k, col]|) over the finite entries, 0 where that maximum is zero or infinite.  grid = ncols, block = kWave.
 __global__ __launch_bounds__(kWave) void k_colexp(const double* __restrict__ Z, int n, int32_t* __restrict__ ze) {
     const int lane = threadIdx.x;
@@ -132,28 +215,20 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
     double* Yt = Y + theta * (int64_t)n * ncols;
 
     const double t0 = tt[0];
-    int bad = (t0 > 0.0 && t0 < INFINITY) ? 0 : 1;                          // the same in every thread
-    double uh[E], ul[E], vh[VL ? 1 : E], vl[VL ? 1 : E], z[E][C];
+    int bad = t0_bad(t0);                                                    // the same in every thread
+    double uh[E], ul[E], z[E][C];
     float zc[E][C];                                                          // sum of lo(L[i, k]) * y_k: the residual is z - zc
-    auto get_v = [&](int e) -> dd { return VL ? dd{s_v[VL ? e : 0][VL ? tid : 0][0], s_v[VL ? e : 0][VL ? tid : 0][1]} : dd{vh[VL ? 0 : e], vl[VL ? 0 : e]}; };
-    auto set_v = [&](int e, dd x) {
-        if (VL) {
-            s_v[VL ? e : 0][VL ? tid : 0][0] = x.h;
-            s_v[VL ? e : 0][VL ? tid : 0][1] = x.l;
-        } else {
-            vh[VL ? 0 : e] = x.h;
-            vl[VL ? 0 : e] = x.l;
-        }
-    };
+    VStore<E, VL> vs{&s_v[0][VL ? tid : 0]};
     if (!bad) {
-        const dd rs = dd_rsqrt(dd{t0, 0.0});
+        const dd rs = t0_rsqrt(t0);
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int i = base + e;
-            const dd u = i < n ? dd_mul_d(rs, tt[i]) : dd{0.0, 0.0};
+            const uv g = generator_from_t(tt, rs, i, n);
+            const dd u = g.u;
             uh[e] = u.h;
             ul[e] = u.l;
-            set_v(e, i > 0 ? u : dd{0.0, 0.0});
+            vs.set(e, g.v);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 z[e][c] = (i < n && c < nc) ? ldexp(Z[(int64_t)(col0 + c) * n + i], -ze[col0 + c]) : 0.0;
@@ -191,13 +266,12 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
             if (tid < 4 && blockIdx.x == 0) steps[(theta * n + k) * 4 + tid] = s_pub[b][tid];
         }
         if (k == n - 1) break;
-        const dd rho = dd_div(dd{s_pub[b][2], s_pub[b][3]}, pu);
-        if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every thread
+        const coeffs co = step_coeffs(pu, dd{s_pub[b][2], s_pub[b][3]});
+        if (!co.ok) {                                                         // the same in every thread
             bad = k + 2;
             break;
         }
-        const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
-        const dd nrho = dd_neg(rho);
+        const dd nrho = dd_neg(co.rho), ic = co.ic;
         if (base + E - 1 > k && base < n) {                                  // the thread still holds elements below the pivot
             dd edge = {0.0, 0.0};
             if (tid > 0) edge = {s_edge[b][tid - 1][0], s_edge[b][tid - 1][1]};
@@ -210,22 +284,20 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
 #pragma unroll
                 for (int c = 0; c < C; ++c) zc[e][c] = fmaf(ulf, yf[c], zc[e][c]);
                 const dd us = e > 0 ? dd{uh[e > 0 ? e - 1 : 0], ul[e > 0 ? e - 1 : 0]} : edge;      // u shifted down by one
-                const dd v = get_v(e);
-                const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
-                const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+                const uv r = rotate(us, vs.get(e), nrho, ic);
                 const bool live = i > k;                                      // at or above the pivot: u[i] keeps L[i, i]
-                uh[e] = live ? un.h : uh[e];
-                ul[e] = live ? un.l : ul[e];
-                set_v(e, vn);
+                uh[e] = live ? r.u.h : uh[e];
+                ul[e] = live ? r.u.l : ul[e];
+                vs.set(e, r.v);
                 if (i == k + 1) {
-                    s_pub[nb][0] = un.h;
-                    s_pub[nb][1] = un.l;
+                    s_pub[nb][0] = r.u.h;
+                    s_pub[nb][1] = r.u.l;
 #pragma unroll
                     for (int c = 0; c < C; ++c) s_pub[nb][4 + c] = z[e][c] - (double)zc[e][c];
                 }
                 if (i == k + 2) {
-                    s_pub[nb][2] = vn.h;
-                    s_pub[nb][3] = vn.l;
+                    s_pub[nb][2] = r.v.h;
+                    s_pub[nb][3] = r.v.l;
                 }
             }
             s_edge[nb][tid][0] = uh[E - 1];
@@ -236,23 +308,14 @@ __global__ __launch_bounds__(kThreads) void k_schur(const double* __restrict__ t
 
     if (blockIdx.x != 0) return;                                             // every chunk of a first column finds the same two numbers
     __syncthreads();
-    double* red = &s_edge[0][0][0];
     double s = 0.0;
     if (!bad) {
 #pragma unroll
         for (int e = 0; e < E; ++e)
             if (base + e < n) s += log(uh[e]);
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
-        if (tid < stride) red[tid] += red[tid + stride];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        sld[theta] = bad ? NAN : red[0];
-        info[theta] = bad;
-    }
+    sum_log_diag_tree(&s_edge[0][0][0], tid, s, bad, sld + theta);
+    if (tid == 0) info[theta] = bad;
 }
 
 // G is (m, n_sets, cols, cols), scaled back by the column exponents ze.  grid = (cols, n_sets, m), block = kWave.
@@ -297,19 +360,18 @@ __device__ __forceinline__ dd wave_fold(dd a) {
 }
 __device__ __forceinline__ bool dd_finite(dd a) { return fabs(a.h) < INFINITY && fabs(a.l) < INFINITY; }
 
-// steps row k < n - 1: {u[k], v[k+1]} -> {rho, 1 / c} by the expressions of k_schur's step, so the words are the ones the generator
+// steps row k < n - 1: {u[k], v[k+1]} -> {rho, 1 / c} by step_coeffs, as in k_schur's step, so the words are the ones the generator
 // was rotated with; row n - 1 keeps u[n-1] = L[n-1, n-1].  Independent rows: no serial chain.  grid = (ceil(n / 256), m), block = 256.
 __global__ __launch_bounds__(256) void k_coeffs(double* __restrict__ steps, int n, const int32_t* __restrict__ info) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     const int64_t theta = blockIdx.y;
     if (k >= n - 1 || info[theta] != 0) return;
     double* st = steps + (theta * n + k) * 4;
-    const dd rho = dd_div(dd{st[2], st[3]}, dd{st[0], st[1]});
-    const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
-    st[0] = rho.h;
-    st[1] = rho.l;
-    st[2] = ic.h;
-    st[3] = ic.l;
+    const coeffs c = step_coeffs(dd{st[0], st[1]}, dd{st[2], st[3]});         // info is 0: k_schur's test of this pair passed
+    st[0] = c.rho.h;
+    st[1] = c.rho.l;
+    st[2] = c.ic.h;
+    st[3] = c.ic.l;
 }
 
 // Levinson's recursion in its normalised form, replaying the (rho, 1 / c) of k_schur<.., R = true> and k_coeffs: A = B = e_0 / sqrt(t_0), then for
@@ -338,7 +400,7 @@ __global__ __launch_bounds__(kThreads) void k_levinson(const double* __restrict_
 #pragma unroll
     for (int e = 0; e < E; ++e) ah[e] = al[e] = bh[e] = bl[e] = 0.0;
     if (tid == 0) {
-        const dd rs = dd_rsqrt(dd{t[theta * n], 0.0});
+        const dd rs = t0_rsqrt(t[theta * n]);
         ah[0] = bh[0] = rs.h;
         al[0] = bl[0] = rs.l;
     }
@@ -369,13 +431,11 @@ __global__ __launch_bounds__(kThreads) void k_levinson(const double* __restrict_
 #pragma unroll
             for (int e = E - 1; e >= 0; --e) {
                 const dd bs = e > 0 ? dd{bh[e > 0 ? e - 1 : 0], bl[e > 0 ? e - 1 : 0]} : edge;       // B shifted down by one
-                const dd a = {ah[e], al[e]};
-                const dd an = dd_mul(dd_add(a, dd_mul(nrho, bs)), ic);
-                const dd bn = dd_mul(dd_add(bs, dd_mul(nrho, a)), ic);
-                ah[e] = an.h;
-                al[e] = an.l;
-                bh[e] = bn.h;
-                bl[e] = bn.l;
+                const uv r = rotate(dd{ah[e], al[e]}, bs, nrho, ic);         // (A, shift(B)) in the roles of (u shifted, v)
+                ah[e] = r.u.h;
+                al[e] = r.u.l;
+                bh[e] = r.v.h;
+                bl[e] = r.v.l;
             }
             s_edge[nb][tid][0] = bh[E - 1];
             s_edge[nb][tid][1] = bl[E - 1];
@@ -707,12 +767,12 @@ __global__ __launch_bounds__(256) void k_panel_load(const double* __restrict__ Z
 }
 
 // k_schur's step without residual columns, for the steps k0 .. min(k0 + kPanelB, n) - 1 of every first column of the launch: the same
-// double-double generator, the same expressions for rho and 1 / c, the same publication through LDS.  The generator state lives in
-// st between launches, (m, 4, kThreads * E): the words u.h, u.l, v.h, v.l of every element; k0 == 0 forms it from t as k_schur does.
+// double-double generator, step_coeffs and rotate, the same sweep and publication through LDS.  The generator state lives in st
+// between launches (state_load / state_store, stride kThreads * E); k0 == 0 forms it from t as k_schur does (generator_from_t).
 // info[theta] is the running failure step: a first column that has failed is skipped by every later launch.  At step k every thread
 // stores its elements of column k of L (u before the rotation), rows k .. n - 1: Ph[theta, k - k0, i] and (float) of the low word in
-// Pl.  The launch that reaches step n - 1 sums log L_jj from the retained u in k_schur's order, so sum_log_diag and info are bit for
-// bit k_schur's.  grid = m, block = kThreads.
+// Pl.  The launch that reaches step n - 1 sums log L_jj from the retained u in k_schur's order (sum_log_diag_tree), so sum_log_diag
+// and info are bit for bit k_schur's.  grid = m, block = kThreads.
 template <int E, bool VL>
 __global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restrict__ t, int n, int k0, double* __restrict__ st,
                                                            double* __restrict__ Ph, float* __restrict__ Pl, double* __restrict__ sld,
@@ -729,42 +789,21 @@ __global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restri
     float* pl = Pl + theta * (int64_t)kPanelB * n;
     const int k1 = min(k0 + kPanelB, n);
 
-    int bad;                                                                  // the same in every thread
-    if (k0 == 0) {
-        const double t0 = tt[0];
-        bad = (t0 > 0.0 && t0 < INFINITY) ? 0 : 1;
-    } else {
-        bad = info[theta];
-    }
-    double uh[E], ul[E], vh[VL ? 1 : E], vl[VL ? 1 : E];
-    auto get_v = [&](int e) -> dd { return VL ? dd{s_v[VL ? e : 0][VL ? tid : 0][0], s_v[VL ? e : 0][VL ? tid : 0][1]} : dd{vh[VL ? 0 : e], vl[VL ? 0 : e]}; };
-    auto set_v = [&](int e, dd x) {
-        if (VL) {
-            s_v[VL ? e : 0][VL ? tid : 0][0] = x.h;
-            s_v[VL ? e : 0][VL ? tid : 0][1] = x.l;
-        } else {
-            vh[VL ? 0 : e] = x.h;
-            vl[VL ? 0 : e] = x.l;
-        }
-    };
+    int bad = k0 == 0 ? t0_bad(tt[0]) : info[theta];                          // the same in every thread
+    double uh[E], ul[E];
+    VStore<E, VL> vs{&s_v[0][VL ? tid : 0]};
     const int b0 = k0 & 1;
     if (!bad) {
         dd rs = {0.0, 0.0};
-        if (k0 == 0) rs = dd_rsqrt(dd{tt[0], 0.0});
+        if (k0 == 0) rs = t0_rsqrt(tt[0]);
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const int i = base + e;
-            dd u, v;
-            if (k0 == 0) {
-                u = i < n ? dd_mul_d(rs, tt[i]) : dd{0.0, 0.0};
-                v = i > 0 ? u : dd{0.0, 0.0};
-            } else {
-                u = {s[i], s[NE + i]};
-                v = {s[2 * NE + i], s[3 * NE + i]};
-            }
+            const uv g = k0 == 0 ? generator_from_t(tt, rs, i, n) : state_load(s, NE, i);
+            const dd u = g.u, v = g.v;
             uh[e] = u.h;
             ul[e] = u.l;
-            set_v(e, v);
+            vs.set(e, v);
             if (i == k0) {
                 s_pub[b0][0] = u.h;
                 s_pub[b0][1] = u.l;
@@ -787,19 +826,15 @@ __global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restri
 #pragma unroll
         for (int e = 0; e < E; ++e) {                                         // column k of L, rows k .. n - 1
             const int i = base + e;
-            if (i >= k && i < n) {
-                pk[i] = uh[e];
-                qk[i] = (float)ul[e];
-            }
+            if (i >= k && i < n) store_column(pk, qk, i, dd{uh[e], ul[e]});
         }
         if (k == n - 1) break;
-        const dd rho = dd_div(dd{s_pub[b][2], s_pub[b][3]}, pu);
-        if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every thread
+        const coeffs co = step_coeffs(pu, dd{s_pub[b][2], s_pub[b][3]});
+        if (!co.ok) {                                                         // the same in every thread
             bad = k + 2;
             break;
         }
-        const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
-        const dd nrho = dd_neg(rho);
+        const dd nrho = dd_neg(co.rho), ic = co.ic;
         if (base + E - 1 > k && base < n) {                                  // the thread still holds elements below the pivot
             dd edge = {0.0, 0.0};
             if (tid > 0) edge = {s_edge[b][tid - 1][0], s_edge[b][tid - 1][1]};
@@ -807,20 +842,18 @@ __global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restri
             for (int e = E - 1; e >= 0; --e) {
                 const int i = base + e;
                 const dd us = e > 0 ? dd{uh[e > 0 ? e - 1 : 0], ul[e > 0 ? e - 1 : 0]} : edge;      // u shifted down by one
-                const dd v = get_v(e);
-                const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
-                const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+                const uv r = rotate(us, vs.get(e), nrho, ic);
                 const bool live = i > k;                                      // at or above the pivot: u[i] keeps L[i, i]
-                uh[e] = live ? un.h : uh[e];
-                ul[e] = live ? un.l : ul[e];
-                set_v(e, vn);
+                uh[e] = live ? r.u.h : uh[e];
+                ul[e] = live ? r.u.l : ul[e];
+                vs.set(e, r.v);
                 if (i == k + 1) {
-                    s_pub[nb][0] = un.h;
-                    s_pub[nb][1] = un.l;
+                    s_pub[nb][0] = r.u.h;
+                    s_pub[nb][1] = r.u.l;
                 }
                 if (i == k + 2) {
-                    s_pub[nb][2] = vn.h;
-                    s_pub[nb][3] = vn.l;
+                    s_pub[nb][2] = r.v.h;
+                    s_pub[nb][3] = r.v.l;
                 }
             }
             s_edge[nb][tid][0] = uh[E - 1];
@@ -832,36 +865,20 @@ __global__ __launch_bounds__(kThreads) void k_schur_panel(const double* __restri
     if (k1 < n) {                                                             // more panels follow: hand the state on
         if (!bad) {
 #pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int i = base + e;
-                const dd v = get_v(e);
-                s[i] = uh[e];
-                s[NE + i] = ul[e];
-                s[2 * NE + i] = v.h;
-                s[3 * NE + i] = v.l;
-            }
+            for (int e = 0; e < E; ++e) state_store(s, NE, base + e, uv{{uh[e], ul[e]}, vs.get(e)});
         }
         if (tid == 0) info[theta] = bad;
         return;
     }
     __syncthreads();
-    double* red = &s_edge[0][0][0];
     double acc = 0.0;
     if (!bad) {
 #pragma unroll
         for (int e = 0; e < E; ++e)
             if (base + e < n) acc += log(uh[e]);
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
-        if (tid < stride) red[tid] += red[tid + stride];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        sld[theta] = bad ? NAN : red[0];
-        info[theta] = bad;
-    }
+    sum_log_diag_tree(&s_edge[0][0][0], tid, acc, bad, sld + theta);
+    if (tid == 0) info[theta] = bad;
 }
 
 // The triangular block of a panel, rows and columns k0 .. k1 - 1 (k1 = min(k0 + kPanelB, n)), for every right-hand-side column: one
@@ -1035,8 +1052,8 @@ __global__ __launch_bounds__(kWave) void k_panel_update(const double* __restrict
 // pivot, tile by tile (k_schur_tiles, one wave per tile): a tile owns kTileR rows and loads kPanelB more above them, which is as far
 // up as kPanelB steps reach, so what its halo lacks never arrives in its own rows.  The generator state lives in HBM, (4, n) doubles
 // per first column (u.h, u.l, v.h, v.l), twice: the tiles of a panel read one buffer, halo included, and write the other.  Nothing
-// holds a whole generator, so n is bounded by the grids and the indices alone.  Every element goes through the expressions of
-// k_schur_panel's step in its order; the panel is stored in its layout, and k_panel_diag and k_panel_update consume it unchanged.
+// holds a whole generator, so n is bounded by the grids and the indices alone.  Every element goes through step_coeffs and rotate in
+// k_schur_panel's order; the panel is stored in its layout (store_column), and k_panel_diag and k_panel_update consume it unchanged.
 // Kernels follow one another in stream order; no workgroup waits for another.
 
 constexpr int kTileE = 8;                          // generator elements per lane of a tile
@@ -1048,28 +1065,20 @@ constexpr int kLeadE = (kPanelB + 1 + kWave - 1) / kWave;      // window element
 // tiles of a panel start at the tile that holds row k0, wherever k0 falls in it.
 static_assert(kTileR >= kWave && kPanelB % kTileE == 0 && kPanelB + 1 <= kLeadE * kWave, "the halo, the own rows and the lead's window fit their lanes");
 
-// The generator state of every first column from t, as k_schur_panel forms it at k0 == 0, and info = 1 for a bad t[0] (0 otherwise).
+// The generator state of every first column from t (generator_from_t, stride n), and info = 1 for a bad t[0] (0 otherwise).
 // grid = (ceil(n / 256), m), block = 256.
 __global__ __launch_bounds__(256) void k_blocked_init(const double* __restrict__ t, int n, double* __restrict__ st, int32_t* __restrict__ info) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int64_t theta = blockIdx.y;
     const double* tt = t + theta * n;
-    const double t0 = tt[0];
-    const int bad = (t0 > 0.0 && t0 < INFINITY) ? 0 : 1;
+    const int bad = t0_bad(tt[0]);
     if (i == 0) info[theta] = bad;
     if (bad || i >= n) return;
-    const dd rs = dd_rsqrt(dd{t0, 0.0});
-    const dd u = dd_mul_d(rs, tt[i]);
-    const dd v = i > 0 ? u : dd{0.0, 0.0};
-    double* s = st + theta * 4 * (int64_t)n;
-    s[i] = u.h;
-    s[(int64_t)n + i] = u.l;
-    s[2 * (int64_t)n + i] = v.h;
-    s[3 * (int64_t)n + i] = v.l;
+    state_store(st + theta * 4 * (int64_t)n, n, i, generator_from_t(tt, t0_rsqrt(tt[0]), i, n));
 }
 
 // The steps k0 .. min(k0 + kPanelB, n - 1) - 1 of every first column on the rows k0 .. min(k0 + kPanelB, n - 1) of its state st:
-// k_schur_panel's expressions for rho, the failure test and 1 / c, and its rotation of the window's rows below the pivot.  Lane l
+// step_coeffs for rho, the failure test and 1 / c, and rotate on the window's rows below the pivot.  Lane l
 // holds the rows k0 + l, k0 + 64 + l, ..; the pivot pair and the element shifted in from the row above come by lane shuffles.  Step k
 // stores {rho.h, rho.l, ic.h, ic.l} at coef[theta, k - k0]; a failure at step k sets info[theta] = k + 2 and ends the first column,
 // which this and every later kernel then skips.  grid = m, block = kWave.
@@ -1085,11 +1094,11 @@ __global__ __launch_bounds__(kWave) void k_schur_lead(int n, int k0, const doubl
 #pragma unroll
     for (int e = 0; e < kLeadE; ++e) {
         const int i = k0 + e * kWave + lane;
-        const bool in = i <= last;
-        uh[e] = in ? s[i] : 0.0;
-        ul[e] = in ? s[(int64_t)n + i] : 0.0;
-        vh[e] = in ? s[2 * (int64_t)n + i] : 0.0;
-        vl[e] = in ? s[3 * (int64_t)n + i] : 0.0;
+        const uv g = i <= last ? state_load(s, n, i) : uv{};
+        uh[e] = g.u.h;
+        ul[e] = g.u.l;
+        vh[e] = g.v.h;
+        vl[e] = g.v.l;
     }
     int bad = 0;
     for (int k = k0; k < last; ++k) {
@@ -1104,13 +1113,12 @@ __global__ __launch_bounds__(kWave) void k_schur_lead(int n, int k0, const doubl
         }
         const dd pu = {__shfl(a0, wu & 63, kWave), __shfl(a1, wu & 63, kWave)};
         const dd pv = {__shfl(a2, wv & 63, kWave), __shfl(a3, wv & 63, kWave)};
-        const dd rho = dd_div(pv, pu);
-        if (!(fabs(rho.h) < 1.0)) {                                          // also a NaN; the same in every lane
+        const coeffs c = step_coeffs(pu, pv);
+        if (!c.ok) {                                                          // the same in every lane
             bad = k + 2;
             break;
         }
-        const dd ic = dd_rsqrt(dd_mul(dd_sub(dd{1.0, 0.0}, rho), dd_add(dd{1.0, 0.0}, rho)));
-        const dd nrho = dd_neg(rho);
+        const dd rho = c.rho, ic = c.ic, nrho = dd_neg(rho);
         if (lane == 0) {
             co[4 * wu] = rho.h;
             co[4 * wu + 1] = rho.l;
@@ -1125,14 +1133,12 @@ __global__ __launch_bounds__(kWave) void k_schur_lead(int n, int k0, const doubl
             const double ph = e > 0 ? __shfl(uh[e > 0 ? e - 1 : 0], kWave - 1, kWave) : 0.0;
             const double pl = e > 0 ? __shfl(ul[e > 0 ? e - 1 : 0], kWave - 1, kWave) : 0.0;
             const dd us = lane == 0 ? dd{ph, pl} : dd{sh, sl};
-            const dd v = {vh[e], vl[e]};
-            const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
-            const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+            const uv r = rotate(us, dd{vh[e], vl[e]}, nrho, ic);
             const bool live = i > k && i <= last;                             // at or above the pivot: u[i] keeps L[i, i]
-            uh[e] = live ? un.h : uh[e];
-            ul[e] = live ? un.l : ul[e];
-            vh[e] = live ? vn.h : vh[e];
-            vl[e] = live ? vn.l : vl[e];
+            uh[e] = live ? r.u.h : uh[e];
+            ul[e] = live ? r.u.l : ul[e];
+            vh[e] = live ? r.v.h : vh[e];
+            vl[e] = live ? r.v.l : vl[e];
         }
     }
     if (bad && lane == 0) info[theta] = bad;
@@ -1142,7 +1148,7 @@ __global__ __launch_bounds__(kWave) void k_schur_lead(int n, int k0, const doubl
 // k0 / kTileR + blockIdx.x owns the rows r0 .. r0 + kTileR - 1 (r0 a multiple of kTileR) and loads from `cur` the rows from
 // r0 - kPanelB on, kTileE consecutive ones per lane in registers; the element a shift brings over a lane boundary comes by a lane
 // shuffle, so a step has no barrier and no LDS.  For each k the tile stores its own rows >= k of column k of L (u before the
-// rotation) as k_schur_panel does, Ph[theta, k - k0, i] and (float) of the low word in Pl, the owner of row k also hi(L_kk) in
+// rotation) by store_column, Ph[theta, k - k0, i] and (float) of the low word in Pl, the owner of row k also hi(L_kk) in
 // dg[theta, k]; then it rotates every element it holds, u only below the pivot.  After s steps the first s rows of the halo are
 // stale; the own rows lie kPanelB below its top and stay exact.  At the end it writes its own rows to `nxt`.
 // Rows above the pivot are unspecified in both state buffers and never used: v is rotated and stored there too (as k_schur does),
@@ -1167,11 +1173,11 @@ __global__ __launch_bounds__(kWave) void k_schur_tiles(int n, int k0, const doub
 #pragma unroll
     for (int e = 0; e < kTileE; ++e) {
         const int i = base + e;
-        const bool in = i >= 0 && i < n;
-        uh[e] = in ? s[i] : 0.0;
-        ul[e] = in ? s[(int64_t)n + i] : 0.0;
-        vh[e] = in ? s[2 * (int64_t)n + i] : 0.0;
-        vl[e] = in ? s[3 * (int64_t)n + i] : 0.0;
+        const uv g = i >= 0 && i < n ? state_load(s, n, i) : uv{};
+        uh[e] = g.u.h;
+        ul[e] = g.u.l;
+        vh[e] = g.v.h;
+        vl[e] = g.v.l;
     }
     const int k1 = min(k0 + kPanelB, n);
     for (int k = k0; k < k1; ++k) {
@@ -1181,8 +1187,7 @@ __global__ __launch_bounds__(kWave) void k_schur_tiles(int n, int k0, const doub
         for (int e = 0; e < kTileE; ++e) {                                    // column k of L, the tile's own rows k .. n - 1
             const int i = base + e;
             if (i >= r0 && i >= k && i < n) {
-                pk[i] = uh[e];
-                qk[i] = (float)ul[e];
+                store_column(pk, qk, i, dd{uh[e], ul[e]});
                 if (i == k) d[k] = uh[e];
             }
         }
@@ -1195,30 +1200,23 @@ __global__ __launch_bounds__(kWave) void k_schur_tiles(int n, int k0, const doub
         for (int e = kTileE - 1; e >= 0; --e) {
             const int i = base + e;
             const dd us = e > 0 ? dd{uh[e > 0 ? e - 1 : 0], ul[e > 0 ? e - 1 : 0]} : edge;          // u shifted down by one
-            const dd v = {vh[e], vl[e]};
-            const dd un = dd_mul(dd_add(us, dd_mul(nrho, v)), ic);
-            const dd vn = dd_mul(dd_add(v, dd_mul(nrho, us)), ic);
+            const uv r = rotate(us, dd{vh[e], vl[e]}, nrho, ic);
             const bool live = i > k;                                          // at or above the pivot: u[i] keeps L[i, i]
-            uh[e] = live ? un.h : uh[e];
-            ul[e] = live ? un.l : ul[e];
-            vh[e] = vn.h;
-            vl[e] = vn.l;
+            uh[e] = live ? r.u.h : uh[e];
+            ul[e] = live ? r.u.l : ul[e];
+            vh[e] = r.v.h;
+            vl[e] = r.v.l;
         }
     }
 #pragma unroll
     for (int e = 0; e < kTileE; ++e) {
         const int i = base + e;
-        if (i >= r0 && i < n) {
-            so[i] = uh[e];
-            so[(int64_t)n + i] = ul[e];
-            so[2 * (int64_t)n + i] = vh[e];
-            so[3 * (int64_t)n + i] = vl[e];
-        }
+        if (i >= r0 && i < n) state_store(so, n, i, uv{{uh[e], ul[e]}, {vh[e], vl[e]}});
     }
 }
 
 // sld[theta] = sum_j log dg[theta, j] in k_schur's order: thread tid adds the logarithms of its E consecutive entries in ascending
-// order, then the binary tree over the threads; NaN for a first column that failed.  With E the size class of n (n <= kMaxN) this is
+// order, then sum_log_diag_tree; NaN for a first column that failed.  With E the size class of n (n <= kMaxN) this is
 // k_schur's sum bit for bit; beyond, E = ceil(n / kThreads).  grid = m, block = kThreads.
 __global__ __launch_bounds__(kThreads) void k_blocked_sld(const double* __restrict__ dg, int n, int E, double* __restrict__ sld,
                                                            const int32_t* __restrict__ info) {
@@ -1233,13 +1231,7 @@ __global__ __launch_bounds__(kThreads) void k_blocked_sld(const double* __restri
         for (int e = 0; e < E; ++e)
             if (base + e < n) s += log(d[base + e]);
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int stride = kThreads / 2; stride > 0; stride >>= 1) {
-        if (tid < stride) red[tid] += red[tid + stride];
-        __syncthreads();
-    }
-    if (tid == 0) sld[theta] = bad ? NAN : red[0];
+    sum_log_diag_tree(red, tid, s, bad, sld + theta);
 }
 
 }  // namespace gt
