@@ -38,13 +38,24 @@ PROTOTYPES = {
     "gsum_toep_gram_blocked": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_predict_blocked": (C.c_int, [_p, _dp, C.c_int64, _dp, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "gsum_toep_blocked_times": (C.c_int, [_p, _dp, C.c_int32]),
+    "gsum_toep_grad_blocked": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, C.c_int64, C.c_int32, _dp, _dp, C.POINTER(C.c_int32),
+                                         _dp, _dp]),
+    "gsum_toep_solve_blocked": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_loo_blocked": (C.c_int, [_p, _dp, C.c_int64, C.c_int64, _dp, C.c_int64, _dp, _dp, C.POINTER(C.c_int32)]),
+    "gsum_toep_levinson_times": (C.c_int, [_p, _dp, C.c_int32]),
 }
 PHASES = ("h2d", "schur", "gram", "d2h")
 GRAD_PHASES = ("h2d", "schur", "levinson", "gram", "diagsums", "solve", "contract", "d2h")    # of grad and solve (gsum_toep_grad_times)
 POST_PHASES = ("h2d", "schur", "levinson", "sums", "cov", "solve", "d2h")                     # of predict and loo (gsum_toep_post_times)
 PANEL_PHASES = ("h2d", "recursion", "diag", "update", "sums", "cov", "d2h")                     # of the panel route (gsum_toep_panel_times)
 BLOCKED_PHASES = ("h2d", "lead", "tiles", "diag", "update", "sums", "cov", "d2h")               # of the blocked route (gsum_toep_blocked_times)
+# of grad, solve and loo with method="blocked" (gsum_toep_levinson_times)
+LEVINSON_PHASES = ("h2d", "lead", "tiles", "diag", "update", "levinson", "gram", "diagsums", "solve", "contract", "d2h")
 METHODS = ("columns", "panel", "blocked")                              # the device schedules of gram and predict
+GRAD_METHODS = ("columns", "blocked")                                  # ... of grad, solve and loo
+_GRAD = {"columns": "gsum_toep_grad", "blocked": "gsum_toep_grad_blocked"}
+_SOLVE = {"columns": "gsum_toep_solve", "blocked": "gsum_toep_solve_blocked"}
+_LOO = {"columns": "gsum_toep_loo", "blocked": "gsum_toep_loo_blocked"}
 _GRAM = {"columns": "gsum_toep_gram", "panel": "gsum_toep_gram_panel", "blocked": "gsum_toep_gram_blocked"}
 _PREDICT = {"columns": "gsum_toep_predict", "panel": "gsum_toep_predict_panel", "blocked": "gsum_toep_predict_blocked"}
 MAX_COLS = 16                                                          # GSUM_TOEP_MAX_COLS
@@ -83,6 +94,14 @@ def check_method(method, name="method"):
     return method
 
 
+def check_grad_method(method, name="method"):
+    """``check_method`` for what works from x = T^-1 e_0 (``toeplitz_grad``, ``toeplitz_solve``, ``toeplitz_loo`` and their kin), which
+    has no panel route: ``name`` is ``method`` or ``toeplitz_grad_method``."""
+    if not isinstance(method, str) or method not in GRAD_METHODS:
+        raise ValueError(f'{name} must be "columns" or "blocked", got {method!r}')
+    return method
+
+
 class DeviceToeplitz(DeviceHandle):
     """A handle of libgsum_toep.so on one device: its stream and its buffers, which grow with the calls."""
 
@@ -116,9 +135,10 @@ class DeviceToeplitz(DeviceHandle):
             _check(self._lib, fn(self._handle(), _d(t), m, n, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info)))
         return G, sld, info
 
-    def grad(self, t, dt, Z, n_sets):
+    def grad(self, t, dt, Z, n_sets, method="columns"):
         """(G, sum_log_diag, info, trace (m, P), H (m, n_sets, P, c, c)) of the first columns t (m, n), their derivative columns dt
-        (m, P, n) and the right-hand sides Z (n, n_sets * c): gsum_toep_grad."""
+        (m, P, n) and the right-hand sides Z (n, n_sets * c): gsum_toep_grad, or gsum_toep_grad_blocked with ``method="blocked"``."""
+        fn = getattr(self._lib, _GRAD[check_grad_method(method)])
         t = np.ascontiguousarray(t, dtype=np.float64)
         dt = np.ascontiguousarray(dt, dtype=np.float64)
         Zf = np.asfortranarray(Z, dtype=np.float64)
@@ -131,13 +151,13 @@ class DeviceToeplitz(DeviceHandle):
         sld = np.empty(m)
         info = np.empty(m, dtype=np.int32)
         with self._lock:
-            _check(self._lib, self._lib.gsum_toep_grad(self._handle(), _d(t), m, n, _d(dt), P, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info),
-                                                       _d(trace), _d(H)))
+            _check(self._lib, fn(self._handle(), _d(t), m, n, _d(dt), P, _d(Zf), n_sets, cols, _d(G), _d(sld), _i32(info), _d(trace), _d(H)))
         return G, sld, info, trace, H
 
-    def solve(self, t, Z, want_x=True):
+    def solve(self, t, Z, want_x=True, method="columns"):
         """(x (m, n) or None, alpha (m, n, c) or None, info): the first column of the inverse and T^-1 Z (Z None: x alone):
-        gsum_toep_solve."""
+        gsum_toep_solve, or gsum_toep_solve_blocked with ``method="blocked"``."""
+        fn = getattr(self._lib, _SOLVE[check_grad_method(method)])
         t = np.ascontiguousarray(t, dtype=np.float64)
         m, n = t.shape
         x = np.empty((m, n)) if want_x else None
@@ -149,8 +169,8 @@ class DeviceToeplitz(DeviceHandle):
             alpha = np.empty((m, n, ncols))
         info = np.empty(m, dtype=np.int32)
         with self._lock:
-            _check(self._lib, self._lib.gsum_toep_solve(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols,
-                                                        None if x is None else _d(x), None if alpha is None else _d(alpha), _i32(info)))
+            _check(self._lib, fn(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, None if x is None else _d(x),
+                                 None if alpha is None else _d(alpha), _i32(info)))
         return x, alpha, info
 
     def predict(self, t, K, Z, want_cov, method="columns"):
@@ -171,8 +191,10 @@ class DeviceToeplitz(DeviceHandle):
                                  None if cov is None else _d(cov), _d(G) if c else None, _d(sld), _i32(info)))
         return quad, cross, cov, G, float(sld[0]), int(info[0])
 
-    def loo(self, t, Z):
-        """(p (m, n), alpha (m, n, c) or None, info): the diagonal of the inverse and T^-1 Z (Z None: p alone): gsum_toep_loo."""
+    def loo(self, t, Z, method="columns"):
+        """(p (m, n), alpha (m, n, c) or None, info): the diagonal of the inverse and T^-1 Z (Z None: p alone): gsum_toep_loo, or
+        gsum_toep_loo_blocked with ``method="blocked"``."""
+        fn = getattr(self._lib, _LOO[check_grad_method(method)])
         t = np.ascontiguousarray(t, dtype=np.float64)
         m, n = t.shape
         p = np.empty((m, n))
@@ -184,9 +206,13 @@ class DeviceToeplitz(DeviceHandle):
             alpha = np.empty((m, n, ncols))
         info = np.empty(m, dtype=np.int32)
         with self._lock:
-            _check(self._lib, self._lib.gsum_toep_loo(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, _d(p),
-                                                      None if alpha is None else _d(alpha), _i32(info)))
+            _check(self._lib, fn(self._handle(), _d(t), m, n, None if Zf is None else _d(Zf), ncols, _d(p), None if alpha is None else _d(alpha),
+                                 _i32(info)))
         return p, alpha, info
+
+    def levinson_times(self, reset=False):
+        """Device milliseconds spent so far by ``grad``, ``solve`` and ``loo`` with ``method="blocked"``, by phase (LEVINSON_PHASES)."""
+        return self._phase_times("gsum_toep_levinson_times", LEVINSON_PHASES, reset)
 
     def blocked_times(self, reset=False):
         """Device milliseconds spent so far by ``gram`` and ``predict`` with ``method="blocked"``, by phase (BLOCKED_PHASES)."""

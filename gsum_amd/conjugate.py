@@ -281,6 +281,7 @@ class ConjugateGaussianProcess:
         self.backend = resolve_backend(backend)
         self.batch_restarts = True   # multi-start fits advance in lock step, objective evaluations batched on the device
         self._fit_structure = None   # "toeplitz" while fit(structure="toeplitz") calibrates
+        self._fit_grad_method = "columns"   # that fit's toeplitz_grad_method=, for the same while
         self.structure_ = None       # "toeplitz" after fit(structure="toeplitz", dense_factor=False): no dense factor is held
         self._toeplitz_method = "columns"   # the last fit's toeplitz_method=: what predict takes with toeplitz_method=None
         self._ctx = None
@@ -596,18 +597,21 @@ class ConjugateGaussianProcess:
         cols = np.stack([column_of_desc(ctx, next(descs) if t is not None else describe_kernel(kernel, 1), X, self.nugget) for t in thetas])
         return X, Z, cols, kernel
 
-    def _lml_grad_structured(self, structure, thetas, X, y):
+    def _lml_grad_structured(self, structure, thetas, X, y, grad_method="columns"):
         """``[(lml, grad), ...]`` of ``structure="toeplitz"``: the first column of every theta's kernel matrix and
         of its derivative by every hyperparameter, one device call for all of them (``toeplitz_grad``), then the host algebra of the
-        dense route.  The values are those of the route without the gradient, bit for bit."""
+        dense route.  The values are those of the route without the gradient, bit for bit.  ``grad_method``: ``toeplitz_grad``'s
+        ``method=`` (with ``"blocked"`` the values are those of ``toeplitz_method="blocked"``)."""
         if structure != "toeplitz":
             raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+        from ._toep_lib import check_grad_method
         from .toeplitz import toeplitz_grad, toeplitz_gradient_columns
+        check_grad_method(grad_method, "toeplitz_grad_method")
         X, Z, cols, kernel = self._structured_inputs(thetas, X, y)
         if kernel.n_dims == 0:
-            return [(float(v), np.zeros(0)) for v in self._lml_structured(structure, thetas, False, X, y)]
+            return [(float(v), np.zeros(0)) for v in self._lml_structured(structure, thetas, False, X, y, grad_method)]
         dts = np.stack([toeplitz_gradient_columns(kernel, X, t) for t in thetas])
-        G, sld, info, trace, H = toeplitz_grad(cols, dts, Z, 1, device=self.device, backend=self.backend)
+        G, sld, info, trace, H = toeplitz_grad(cols, dts, Z, 1, device=self.device, backend=self.backend, method=grad_method)
         vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
         out = []
         for i, t in enumerate(thetas):
@@ -675,17 +679,20 @@ class ConjugateGaussianProcess:
             raise ValueError("Unknown optimizer %s." % self.optimizer)
         return theta_opt, func_min
 
-    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None, eval_gradient=False, toeplitz_method="columns"):
+    def log_marginal_likelihood_batch(self, thetas, X=None, y=None, structure=None, eval_gradient=False, toeplitz_method="columns",
+                                      toeplitz_grad_method="columns"):
         """``log_marginal_likelihood(theta, eval_gradient=True)`` for several ``theta`` at once: [(lml, grad), ...].  The
         evaluations are independent and go to the device as one pipelined batch (gsum_lml_grad_batch); every entry equals
         the single call's result bit for bit.  ``structure="toeplitz"``: the values alone, as an array with one entry per theta
         (``log_marginal_likelihood(theta, structure="toeplitz")``), from one device call; with ``eval_gradient=True`` the dense
         batch's [(lml, grad), ...] from one device call (DESIGN.md section 19).  ``eval_gradient`` is read on that route alone;
-        ``toeplitz_method`` (``toeplitz_gram``'s ``method=``) on the values alone."""
+        ``toeplitz_method`` (``toeplitz_gram``'s ``method=``) on the values alone, ``toeplitz_grad_method`` (``toeplitz_grad``'s
+        ``method=``) with ``eval_gradient=True`` alone: a separate keyword, because the gradient has no panel
+        route and keeps its own limit unless it is asked for ``"blocked"``."""
         if structure is not None:
             thetas = [np.atleast_1d(np.asarray(t, dtype=float)) for t in thetas]
             if eval_gradient:
-                return self._lml_grad_structured(structure, thetas, X, y)
+                return self._lml_grad_structured(structure, thetas, X, y, toeplitz_grad_method)
             return self._lml_structured(structure, thetas, False, X, y, toeplitz_method)
         self._check_decomposition()
         base = self._active_kernel()
@@ -723,7 +730,8 @@ class ConjugateGaussianProcess:
             ids = sorted(pending)
             try:
                 if self._fit_structure is not None:
-                    vals = self.log_marginal_likelihood_batch([pending[i] for i in ids], structure=self._fit_structure, eval_gradient=True)
+                    vals = self.log_marginal_likelihood_batch([pending[i] for i in ids], structure=self._fit_structure, eval_gradient=True,
+                                                              toeplitz_grad_method=self._fit_grad_method)
                 else:
                     vals = self.log_marginal_likelihood_batch([pending[i] for i in ids])
             except BaseException as exc:   # noqa: BLE001 -- handed to every waiting thread
@@ -798,9 +806,10 @@ class ConjugateGaussianProcess:
             def obj_func(theta, eval_gradient=True):                                   # models.py:634-640
                 if self._fit_structure is not None:                                   # the structured route: the batch of one
                     if eval_gradient:
-                        lml, grad = self.log_marginal_likelihood_batch([theta], structure=self._fit_structure, eval_gradient=True)[0]
+                        lml, grad = self.log_marginal_likelihood_batch([theta], structure=self._fit_structure, eval_gradient=True,
+                                                                       toeplitz_grad_method=self._fit_grad_method)[0]
                         return -lml, -grad
-                    return -float(self.log_marginal_likelihood_batch([theta], structure=self._fit_structure)[0])
+                    return -float(self.log_marginal_likelihood_batch([theta], structure=self._fit_structure, toeplitz_method=self._fit_grad_method)[0])
                 if eval_gradient:
                     lml, grad = self.log_marginal_likelihood(theta, eval_gradient=True)
                     return -lml, -grad
@@ -824,7 +833,7 @@ class ConjugateGaussianProcess:
             return -float(values[best])
         return None
 
-    def fit(self, X, y, structure=None, dense_factor=True, toeplitz_method="columns"):
+    def fit(self, X, y, structure=None, dense_factor=True, toeplitz_method="columns", toeplitz_grad_method="columns"):
         """``structure="toeplitz"``: every objective evaluation of the calibration -- the single start's and the lock-step restarts' --
         runs on the structured route (``log_marginal_likelihood_batch(.., structure="toeplitz", eval_gradient=True)``); X must be a
         uniform one-dimensional grid and the kernel stationary, checked before the optimiser starts.  The final factorisation, the
@@ -835,10 +844,14 @@ class ConjugateGaussianProcess:
         ``toeplitz_method`` (``toeplitz_predict``'s ``method=``): a fit with ``dense_factor=False`` remembers it for ``predict`` and
         ``sample_y``; the calibration, with at most one set of columns, stays on the column route.  With ``"blocked"`` (DESIGN.md
         section 23) the final ``toeplitz_gram`` takes that route too, so ``optimizer=None`` with ``dense_factor=False`` fits and
-        predicts beyond ``toeplitz_max_n()``; the gradient of a calibration keeps that limit and says so."""
+        predicts beyond ``toeplitz_max_n()``; the gradient of a calibration keeps that limit and says so, unless
+        ``toeplitz_grad_method="blocked"`` (``toeplitz_grad``'s ``method=``; read with ``structure="toeplitz"``)
+        sends every objective evaluation down the blocked route and the tiled replay: with both keywords ``"blocked"`` and
+        ``dense_factor=False`` a fit with an optimiser, ``predict`` and ``loo`` run beyond ``toeplitz_max_n()``."""
         self._check_decomposition()
-        from ._toep_lib import check_method
+        from ._toep_lib import check_grad_method, check_method
         self._toeplitz_method = check_method(toeplitz_method, "toeplitz_method")
+        check_grad_method(toeplitz_grad_method, "toeplitz_grad_method")
         if not dense_factor and structure != "toeplitz":
             raise ValueError('dense_factor=False needs structure="toeplitz": there is no other route without the dense factor')
         if structure is not None:
@@ -853,11 +866,11 @@ class ConjugateGaussianProcess:
                 raise NotImplementedError("the Toeplitz path needs a stationary kernel: this one has a DotProduct leaf")
             if self._many_curves(y):
                 raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
-        self._fit_structure = structure
+        self._fit_structure, self._fit_grad_method = structure, toeplitz_grad_method
         try:
             return self._fit_dense_after_calibration(X, y, dense_factor)
         finally:
-            self._fit_structure = None
+            self._fit_structure, self._fit_grad_method = None, "columns"
 
     def _fit_dense_after_calibration(self, X, y, dense_factor=True):
         self.kernel_ = clone(self._default_kernel if self.kernel is None else self.kernel)   # models.py:685-688
@@ -947,22 +960,28 @@ class ConjugateGaussianProcess:
         center = self.center_ if self._fit else self.center0
         return self.basis(X) @ center
 
-    def loo(self, y=None, structure=None):
+    def loo(self, y=None, structure=None, toeplitz_method=None):
         """The plug-in leave-one-out predictions of the fitted process at its training points (``LooResult``; loo.py): mean =
         ``center_``, cov = ``cov_factor_`` (R + nugget I), whose factor is sqrt(``cov_factor_``) times the one ``fit`` holds.  ``y``,
         (n,) or (n, n_curves), defaults to the training curves.  ``structure="toeplitz"`` (or ``structure_`` after
-        ``fit(dense_factor=False)``): ``toeplitz_loo`` of the first column ``cov_factor_ * t`` instead, without the factor."""
+        ``fit(dense_factor=False)``): ``toeplitz_loo`` of the first column ``cov_factor_ * t`` instead, without the factor.
+        ``toeplitz_method``: ``toeplitz_loo``'s ``method=`` on that route; None takes the last fit's (``"blocked"`` if the fit
+        remembered it, the column route otherwise: there is no panel route from the inverse's first column)."""
         if isinstance(self, ConjugateStudentProcess):
             raise NotImplementedError("loo is the Gaussian leave-one-out; a Student-t leave-one-out is not provided")
         structure = self._structure_of(structure)
         if structure is not None:
             if not self._fit:
                 raise ValueError("loo needs a fitted process: call fit first")
+            from ._toep_lib import check_grad_method
             from .toeplitz import toeplitz_loo
+            if toeplitz_method is None:
+                toeplitz_method = "blocked" if self._toeplitz_method == "blocked" else "columns"
+            check_grad_method(toeplitz_method, "toeplitz_method")
             X = np.asarray(self.X_train_, dtype=float)
             t = self._structured_column(self._context(), describe_kernel(self.kernel_, X.shape[1]), X)
             return toeplitz_loo(float(np.squeeze(self.cov_factor_)) * t, self.y_train_ if y is None else y, self.mean(X),
-                                device=self.device, backend=self.backend)
+                                device=self.device, backend=self.backend, method=toeplitz_method)
         from .loo import loo_from_factor
         L, y, mean = self._plug_in(y, "loo")
         return loo_from_factor(L, y, mean=mean, device=self.device, backend=self.backend)

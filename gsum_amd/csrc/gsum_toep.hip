@@ -23,6 +23,8 @@ enum PostPhase { kPH2D = kAllPhases, kPSchur, kPLevinson, kPSums, kPCov, kPSolve
 enum PanelPhase { kNH2D = kEveryPhase, kNRecursion, kNDiag, kNUpdate, kNSums, kNCov, kND2H, kTotalPhases };
 // the phases of gsum_toep_gram_blocked and gsum_toep_predict_blocked (gsum_toep_blocked_times), after those
 enum BlockedPhase { kBH2D = kTotalPhases, kBLead, kBTiles, kBDiag, kBUpdate, kBSums, kBCov, kBD2H, kGrandPhases };
+// the phases of gsum_toep_grad_blocked, gsum_toep_solve_blocked and gsum_toep_loo_blocked (gsum_toep_levinson_times), after those
+enum LevinsonPhase { kLH2D = kGrandPhases, kLLead, kLTiles, kLDiag, kLUpdate, kLLevinson, kLGram, kLDiagsums, kLSolve, kLContract, kLD2H, kUltimatePhases };
 
 static_assert((GSUM_TOEP_BLOCKED_MAX_N - gt::kPanelB + 15) / 16 <= 65535 && (GSUM_TOEP_BLOCKED_MAX_N + 31) / 32 <= 65535,
               "k_panel_update's and k_panel_load's grid y at the blocked route's limit");
@@ -34,7 +36,7 @@ constexpr size_t kPanelBudget = (size_t)1 << 30;
 
 }  // namespace
 
-struct gsum_toep : TimedHandle<kGrandPhases> {
+struct gsum_toep : TimedHandle<kUltimatePhases> {
     DevBuf<double, true> t, Z, Y, G, sld;
     DevBuf<int32_t, true> info, ze;
     DevBuf<double, true> dt, steps, xd, xf, sd, trace, W, As, Aout, Q, H;      // the gradient path's
@@ -42,6 +44,7 @@ struct gsum_toep : TimedHandle<kGrandPhases> {
     DevBuf<double, true> Ph, Pst;                                              // the panel route's: a panel's high words, the generator state
     DevBuf<float, true> Pl, Zc;                                                // ... its low words, the correction words beside Y
     DevBuf<double, true> Bst, Bco, Bdg;                                        // the blocked route's: two generator states, a panel's coefficients, diag(L)
+    DevBuf<double, true> Lst;                                                  // the tiled replay's: the two states of A and B
 };
 
 namespace {
@@ -142,9 +145,12 @@ void check_scale(const char* who, const double* t, int64_t m, int64_t n, const c
 }
 
 // Both, after the counts, for grad and solve.  gram runs the two with its set checks between them, in the order it always refused in.
-void check_first_columns(const char* who, const double* t, int64_t m, int64_t n) {
+void check_first_columns(const char* who, const double* t, int64_t m, int64_t n, bool blocked = false) {
     if (m < 1 || n < 1) throw Error(std::string(who) + ": m and n must be >= 1, got " + std::to_string(m) + ", " + std::to_string(n));
-    check_order(who, n);
+    if (blocked)
+        check_order(who, n, GSUM_TOEP_BLOCKED_MAX_N, "the grids of the panel kernels");
+    else
+        check_order(who, n);
     check_scale(who, t, m, n);
 }
 
@@ -167,78 +173,6 @@ void launch_solve(gsum_toep* h, int n, int ncols, int64_t cnt, const double* xd,
     SL_LAUNCHED("k_gs_first");
     gt::k_gs_second<<<grid, gt::kWave, 0, h->stream>>>(xd, n, h->W.p, h->ze.p, ncols, info, h->As.p, alpha_out);
     SL_LAUNCHED("k_gs_second");
-}
-
-// The phases a call of solve_columns is charged to: gsum_toep_solve's are the gradient path's, gsum_toep_loo's the posterior's.
-struct SolvePhases {
-    int h2d, schur, levinson, solve, d2h;
-};
-
-// The body of gsum_toep_solve and gsum_toep_loo (`who`): x = T^-1 e_0 of m first columns by the recursion on one column of zeros and
-// Levinson's replay, then alpha = T^-1 Z (alpha_out not null) and p = diag(T^-1) (p_out not null) from it.
-void solve_columns(const char* who, const SolvePhases& ph, gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols64,
-                   double* x_out, double* alpha_out, double* p_out, int32_t* info_out) {
-    const std::string name(who);
-    if (alpha_out && ncols64 < 1) throw Error(name + ": ncols must be >= 1, got " + std::to_string(ncols64));
-    check_first_columns(who, t, m, n);
-    const int64_t nc = alpha_out ? ncols64 : 0;
-    if (nc > (((int64_t)1 << 31) - 1) / n) throw Error(name + ": n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
-    const int ncols = (int)nc;
-    const size_t per_theta = (size_t)n * std::max(ncols, 1);
-    const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
-    run(h, [&] {
-        h->t.reserve((size_t)m * n);
-        h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
-        h->ze.reserve((size_t)ncols + 1);
-        h->Y.reserve((size_t)n * step);
-        h->steps.reserve((size_t)4 * n * step);
-        h->xd.reserve((size_t)2 * n * step);
-        h->xf.reserve((size_t)n * m);
-        h->sld.reserve((size_t)m);
-        h->info.reserve((size_t)m);
-        if (p_out) h->pd.reserve((size_t)n * m);
-        if (ncols) {
-            h->As.reserve(per_theta * step);
-            h->Aout.reserve(per_theta * step);
-            h->W.reserve(4 * per_theta * step);
-        }
-        hipStream_t st = h->stream;
-        // the recursion needs no right-hand side here: it runs on one column of zeros, kept after the ncols of Z
-        double* zero = h->Z.p + (size_t)n * ncols;
-        int32_t* zero_e = h->ze.p + ncols;
-        timed(h, ph.h2d, [&] {
-            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
-            if (ncols) SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * n * ncols, hipMemcpyHostToDevice, st));
-            SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
-            SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
-        });
-        if (ncols) timed(h, ph.schur, [&] { launch_colexp(h, (int)n, ncols); });
-        for (int64_t lo = 0; lo < m; lo += step) {
-            const int64_t cnt = std::min(step, m - lo);
-            const double* tl = h->t.p + lo * n;
-            int32_t* il = h->info.p + lo;
-            timed(h, ph.schur, [&] { launch_schur<true>(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
-            timed(h, ph.levinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
-            if (p_out)
-                timed(h, ph.solve, [&] {
-                    with_size_class((int)n, [&](auto k) {
-                        gt::k_invdiag<decltype(k)::E><<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->xd.p, (int)n, il, h->pd.p + lo * n);
-                    });
-                    SL_LAUNCHED("k_invdiag");
-                });
-            if (ncols) {
-                timed(h, ph.solve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
-                timed(h, ph.d2h, [&] {
-                    SL_CHECK(hipMemcpyAsync(alpha_out + (size_t)lo * per_theta, h->Aout.p, sizeof(double) * per_theta * cnt, hipMemcpyDeviceToHost, st));
-                });
-            }
-        }
-        timed(h, ph.d2h, [&] {
-            if (x_out) SL_CHECK(hipMemcpyAsync(x_out, h->xf.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
-            if (p_out) SL_CHECK(hipMemcpyAsync(p_out, h->pd.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
-            SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-        });
-    });
 }
 
 // ---- the panel route ----
@@ -319,24 +253,39 @@ void reserve_blocked(gsum_toep* h, int64_t n, int64_t ncols, int64_t step) {
     h->Bdg.reserve((size_t)n * step);
 }
 
+// The phases the blocked recursion charges: the blocked clock's, or the tiled replay's for the entry points that go on to x.
+struct BlockedPhases {
+    int lead, tiles, diag, update;
+};
+constexpr BlockedPhases kBlockedClock = {kBLead, kBTiles, kBDiag, kBUpdate};
+constexpr BlockedPhases kLevinsonClock = {kLLead, kLTiles, kLDiag, kLUpdate};
+
 // panel_solve with the recursion of a panel split into its lead and its tiles: per panel k_schur_lead, k_schur_tiles (from one state
-// buffer into the other), then the panel route's triangular block and trailing update on the panel the tiles stored.
-void blocked_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+// buffer into the other), then the panel route's triangular block and trailing update on the panel the tiles stored.  ncols == 0:
+// the recursion alone.  keep, (cnt, n, 4), if not null receives what the replay needs in k_coeffs' layout: the lead overwrites its
+// panel's (rho, 1 / c) at the next panel, so each panel's rows are moved there after its lead, and row n - 1 takes both words of
+// u[n-1] = L[n-1, n-1] from the final state.  A call without keep pays for no copy.
+void blocked_recursion(gsum_toep* h, const BlockedPhases& ph, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info, double* keep) {
     hipStream_t st = h->stream;
-    load_residuals(h, n, ncols, cnt, kBUpdate);
+    const size_t row = sizeof(double) * 4 * n;                                 // of a first column in keep, and of a plane quadruple of the state
+    if (ncols) load_residuals(h, n, ncols, cnt, ph.update);
     double* cur = h->Bst.p;
     double* nxt = cur + (size_t)4 * n * cnt;
-    timed(h, kBTiles, [&] {
+    timed(h, ph.tiles, [&] {
         gt::k_blocked_init<<<dim3((unsigned)((n + 255) / 256), (unsigned)cnt), 256, 0, st>>>(t, n, cur, info);
         SL_LAUNCHED("k_blocked_init");
     });
     int panels = 0;
     for (int k0 = 0; k0 < n; k0 += gt::kPanelB) {
-        timed(h, kBLead, [&] {
+        timed(h, ph.lead, [&] {
             gt::k_schur_lead<<<(unsigned)cnt, gt::kWave, 0, st>>>(n, k0, cur, h->Bco.p, info);
             SL_LAUNCHED("k_schur_lead");
+            const int lead_steps = std::min(k0 + gt::kPanelB, n - 1) - k0;     // the rows k0 .. of keep
+            if (keep && lead_steps > 0)
+                SL_CHECK(hipMemcpy2DAsync(keep + (size_t)4 * k0, row, h->Bco.p, sizeof(double) * 4 * gt::kPanelB, sizeof(double) * 4 * lead_steps,
+                                          (size_t)cnt, hipMemcpyDeviceToDevice, st));
         });
-        timed(h, kBTiles, [&] {
+        timed(h, ph.tiles, [&] {
             const dim3 grid((unsigned)((n - 1) / gt::kTileR - k0 / gt::kTileR + 1), (unsigned)cnt);      // the tiles from the pivot's on
             gt::k_schur_tiles<<<grid, gt::kWave, 0, st>>>(n, k0, cur, nxt, h->Bco.p, h->Ph.p, h->Pl.p, h->Bdg.p, info);
             SL_LAUNCHED("k_schur_tiles");
@@ -344,14 +293,238 @@ void blocked_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt,
         // both buffers are required: a tile's halo is its upper neighbour's own rows, and nothing orders the tiles of one launch, so a
         // tile may load after its neighbour has stored.  No test sees a single buffer fail (the hardware starts neighbours together).
         std::swap(cur, nxt);
-        apply_panel(h, n, k0, ncols, cnt, info, kBDiag, kBUpdate);
+        if (ncols) apply_panel(h, n, k0, ncols, cnt, info, ph.diag, ph.update);
         // a large n has thousands of panels with four event pairs each: settle them every kBlockedSettle panels, which costs one
         // stream synchronisation each time (64 of them at n = 2^20, none before the last panel at n <= 16384)
         if (++panels % kBlockedSettle == 0) settle(h);
     }
-    timed(h, kBTiles, [&] {
+    timed(h, ph.tiles, [&] {
         gt::k_blocked_sld<<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->Bdg.p, n, generator_elements(n), sld, info);
         SL_LAUNCHED("k_blocked_sld");
+        if (keep)                                                              // the state keeps L_ii in u at and above the pivot: planes 0 and 1, row n - 1
+            SL_CHECK(hipMemcpy2DAsync(keep + (size_t)4 * (n - 1), row, cur + (n - 1), row, sizeof(double), (size_t)cnt, hipMemcpyDeviceToDevice, st));
+        if (keep)
+            SL_CHECK(hipMemcpy2DAsync(keep + (size_t)4 * (n - 1) + 1, row, cur + (size_t)n + (n - 1), row, sizeof(double), (size_t)cnt, hipMemcpyDeviceToDevice, st));
+    });
+}
+
+void blocked_solve(gsum_toep* h, const double* t, int n, int ncols, int64_t cnt, double* sld, int32_t* info) {
+    blocked_recursion(h, kBlockedClock, t, n, ncols, cnt, sld, info, nullptr);
+}
+
+// ---- the tiled replay ----
+
+// What the entry points that go on to x keep per first column beside the blocked route's: steps, the two states of A and B, xd, xf
+// and the diagonal sums; per right-hand side W, As, with P derivative columns Q, and for the host alpha.
+size_t levinson_bytes(int64_t n, int64_t ncols, int64_t P, bool alpha_out) {
+    return ((size_t)(4 + 2 * 4 + 2 + 1 + 2) * n + (size_t)n * ncols * (4 + 1 + 2 * P + (alpha_out ? 1 : 0))) * sizeof(double);
+}
+
+// launch_levinson on tiles: the rows of steps the blocked recursion kept are (rho, 1 / c) already.  Per panel of kPanelB steps the
+// tiles 0 .. (its last step) / kTileR, from one state into the other; both are zero-filled first, and the first panel always runs
+// (it sets A[0] = B[0], which is all of n = 1).  Both states are required for the reason blocked_recursion gives.
+void tiled_levinson(gsum_toep* h, const double* t, int n, int64_t cnt, const double* steps, double* xd, double* xf, double* sld, int32_t* info) {
+    hipStream_t st = h->stream;
+    double* cur = h->Lst.p;
+    double* nxt = cur + (size_t)4 * n * cnt;
+    timed(h, kLLevinson, [&] { SL_CHECK(hipMemsetAsync(cur, 0, sizeof(double) * 2 * 4 * n * cnt, st)); });
+    int panels = 0, k0 = 0;
+    do {
+        timed(h, kLLevinson, [&] {
+            const dim3 grid((unsigned)(std::min(k0 + gt::kPanelB, n - 1) / gt::kTileR + 1), (unsigned)cnt);
+            gt::k_levinson_tiles<<<grid, gt::kWave, 0, st>>>(t, n, k0, cur, nxt, steps, info);
+            SL_LAUNCHED("k_levinson_tiles");
+        });
+        std::swap(cur, nxt);
+        if (++panels % kBlockedSettle == 0) settle(h);
+    } while ((k0 += gt::kPanelB) < n - 1);
+    timed(h, kLLevinson, [&] {
+        gt::k_levinson_finish<<<(unsigned)cnt, gt::kThreads, 0, st>>>(cur, n, steps, xd, xf, sld, info);
+        SL_LAUNCHED("k_levinson_finish");
+    });
+}
+
+// The phases a call of solve_columns is charged to: gsum_toep_solve's are the gradient path's, gsum_toep_loo's the posterior's, and
+// those of the two blocked entry points the tiled replay's, with the phases of the blocked recursion (null: the column route).
+struct SolvePhases {
+    int h2d, schur, levinson, solve, d2h;
+    const BlockedPhases* blocked = nullptr;
+};
+
+// The body of gsum_toep_solve, gsum_toep_loo and their blocked namesakes (`who`): x = T^-1 e_0 of m first columns by the recursion
+// and Levinson's replay, then alpha = T^-1 Z (alpha_out not null) and p = diag(T^-1) (p_out not null) from it.  The recursion needs
+// no right-hand side: the column route runs it on one column of zeros, the blocked route without columns.
+void solve_columns(const char* who, const SolvePhases& ph, gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols64,
+                   double* x_out, double* alpha_out, double* p_out, int32_t* info_out) {
+    const std::string name(who);
+    const bool blocked = ph.blocked != nullptr;
+    if (alpha_out && ncols64 < 1) throw Error(name + ": ncols must be >= 1, got " + std::to_string(ncols64));
+    check_first_columns(who, t, m, n, blocked);
+    const int64_t nc = alpha_out ? ncols64 : 0;
+    if (nc > (((int64_t)1 << 31) - 1) / n) throw Error(name + ": n * ncols must be < 2^31, got " + std::to_string(n) + " x " + std::to_string(nc));
+    const int ncols = (int)nc;
+    const size_t per_theta = (size_t)n * std::max(ncols, 1);
+    const int64_t step = blocked ? columns_per_launch(m, blocked_bytes(n, 0) + levinson_bytes(n, ncols, 0, true), kPanelBudget)
+                                 : columns_per_launch(m, 2 * per_theta * sizeof(double));
+    run(h, [&] {
+        h->t.reserve((size_t)m * n);
+        h->Z.reserve(per_theta + n);                                       // the right-hand sides, then one column of zeros
+        h->ze.reserve((size_t)ncols + 1);
+        if (blocked) {
+            reserve_blocked(h, n, 0, step);
+            h->Lst.reserve((size_t)2 * 4 * n * step);
+        } else {
+            h->Y.reserve((size_t)n * step);
+        }
+        h->steps.reserve((size_t)4 * n * step);
+        h->xd.reserve((size_t)2 * n * step);
+        h->xf.reserve((size_t)n * m);
+        h->sld.reserve((size_t)m);
+        h->info.reserve((size_t)m);
+        if (p_out) h->pd.reserve((size_t)n * m);
+        if (ncols) {
+            h->As.reserve(per_theta * step);
+            h->Aout.reserve(per_theta * step);
+            h->W.reserve(4 * per_theta * step);
+        }
+        hipStream_t st = h->stream;
+        // the column route's recursion runs on one column of zeros, kept after the ncols of Z
+        double* zero = h->Z.p + (size_t)n * ncols;
+        int32_t* zero_e = h->ze.p + ncols;
+        timed(h, ph.h2d, [&] {
+            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+            if (ncols) SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * n * ncols, hipMemcpyHostToDevice, st));
+            if (!blocked) {
+                SL_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * n, st));
+                SL_CHECK(hipMemsetAsync(zero_e, 0, sizeof(int32_t), st));
+            }
+        });
+        if (ncols) timed(h, ph.schur, [&] { launch_colexp(h, (int)n, ncols); });
+        for (int64_t lo = 0; lo < m; lo += step) {
+            const int64_t cnt = std::min(step, m - lo);
+            const double* tl = h->t.p + lo * n;
+            int32_t* il = h->info.p + lo;
+            if (blocked) {
+                blocked_recursion(h, *ph.blocked, tl, (int)n, 0, cnt, h->sld.p + lo, il, h->steps.p);
+                tiled_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il);
+            } else {
+                timed(h, ph.schur, [&] { launch_schur<true>(h, tl, (int)n, zero, zero_e, 1, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, ph.levinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p + lo * n, h->sld.p + lo, il); });
+            }
+            if (p_out)
+                timed(h, ph.solve, [&] {
+                    if (blocked)
+                        gt::k_invdiag_n<<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->xd.p, (int)n, generator_elements(n), il, h->pd.p + lo * n);
+                    else
+                        with_size_class((int)n, [&](auto k) {
+                            gt::k_invdiag<decltype(k)::E><<<(unsigned)cnt, gt::kThreads, 0, st>>>(h->xd.p, (int)n, il, h->pd.p + lo * n);
+                        });
+                    SL_LAUNCHED("k_invdiag");
+                });
+            if (ncols) {
+                timed(h, ph.solve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, h->Aout.p); });
+                timed(h, ph.d2h, [&] {
+                    SL_CHECK(hipMemcpyAsync(alpha_out + (size_t)lo * per_theta, h->Aout.p, sizeof(double) * per_theta * cnt, hipMemcpyDeviceToHost, st));
+                });
+            }
+        }
+        timed(h, ph.d2h, [&] {
+            if (x_out) SL_CHECK(hipMemcpyAsync(x_out, h->xf.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
+            if (p_out) SL_CHECK(hipMemcpyAsync(p_out, h->pd.p, sizeof(double) * m * n, hipMemcpyDeviceToHost, st));
+            SL_CHECK(hipMemcpyAsync(info_out, h->info.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+        });
+    });
+}
+
+// The phases a call of grad_route is charged to: gsum_toep_grad's are the gradient path's, gsum_toep_grad_blocked's the tiled
+// replay's, with the phases of the blocked recursion (null: the column route).
+struct GradPhases {
+    int h2d, schur, levinson, gram, diag, solve, contract, d2h;
+    const BlockedPhases* blocked = nullptr;
+};
+
+// The body of gsum_toep_grad and gsum_toep_grad_blocked (`who`).  They differ in the recursion that leaves Y, sum_log_diag, info and
+// the coefficients, in the replay that leaves x, and in the limit and the memory that come with those; the kernels from x on are one.
+void grad_route(const char* who, const GradPhases& ph, gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z,
+                int64_t n_sets, int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out) {
+    const std::string name(who);
+    const bool blocked = ph.blocked != nullptr;
+    if (!h || !t || !dt || !Z || !G_out || !sld_out || !info_out || !trace_out || !H_out) throw Error(name + ": null pointer argument");
+    if (n_sets < 1) throw Error(name + ": n_sets must be >= 1, got " + std::to_string(n_sets));
+    if (P < 1 || P > 65535) throw Error(name + ": P must be between 1 and 65535, got " + std::to_string(P));
+    check_cols(who, cols);
+    check_first_columns(who, t, m, n, blocked);
+    check_sets(who, n, n_sets, cols);
+    if ((int64_t)cols * cols * P > ((int64_t)1 << 31) - 1) throw Error(name + ": cols * cols * P must be < 2^31");
+    const int ncols = (int)(n_sets * cols);
+    const size_t per_theta = (size_t)n * ncols;                                // doubles of Y, and of alpha, per first column
+    const int64_t step = blocked ? columns_per_launch(m, blocked_bytes(n, ncols) + levinson_bytes(n, ncols, P, false), kPanelBudget)
+                                 : columns_per_launch(m, 2 * per_theta * sizeof(double));
+    const size_t gsz = (size_t)n_sets * cols * cols, hsz = gsz * (size_t)P;
+    run(h, [&] {
+        h->t.reserve((size_t)m * n);
+        h->dt.reserve((size_t)m * P * n);
+        h->Z.reserve(per_theta);
+        if (blocked) {
+            reserve_blocked(h, n, ncols, step);
+            h->Lst.reserve((size_t)2 * 4 * n * step);
+        } else {
+            h->Y.reserve(per_theta * step);
+        }
+        h->As.reserve(per_theta * step);
+        h->W.reserve(4 * per_theta * step);
+        h->Q.reserve(2 * per_theta * step * P);
+        h->steps.reserve((size_t)4 * n * step);
+        h->xd.reserve((size_t)2 * n * step);
+        h->xf.reserve((size_t)n * step);
+        h->sd.reserve((size_t)2 * n * step);
+        h->G.reserve(gsz * m);
+        h->H.reserve(hsz * m);
+        h->trace.reserve((size_t)m * P);
+        h->sld.reserve((size_t)m);
+        h->info.reserve((size_t)m);
+        h->ze.reserve((size_t)ncols);
+        hipStream_t st = h->stream;
+        timed(h, ph.h2d, [&] {
+            SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(h->dt.p, dt, sizeof(double) * m * P * n, hipMemcpyHostToDevice, st));
+            SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
+        });
+        timed(h, ph.schur, [&] { launch_colexp(h, (int)n, ncols); });
+        for (int64_t lo = 0; lo < m; lo += step) {
+            const int64_t cnt = std::min(step, m - lo);
+            const double* tl = h->t.p + lo * n;
+            int32_t* il = h->info.p + lo;
+            if (blocked) {
+                blocked_recursion(h, *ph.blocked, tl, (int)n, ncols, cnt, h->sld.p + lo, il, h->steps.p);
+                tiled_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p, h->sld.p + lo, il);
+            } else {
+                timed(h, ph.schur, [&] { launch_schur<true>(h, tl, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
+                timed(h, ph.levinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p, h->sld.p + lo, il); });
+            }
+            timed(h, ph.gram, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
+            timed(h, ph.diag, [&] {
+                gt::k_diagsums<<<dim3((unsigned)n, (unsigned)cnt), gt::kWave, 0, st>>>(h->xd.p, (int)n, il, h->sd.p);
+                SL_LAUNCHED("k_diagsums");
+                gt::k_traces<<<dim3((unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->sd.p, h->dt.p + lo * P * n, (int)n, (int)P, il,
+                                                                                     h->trace.p + lo * P);
+                SL_LAUNCHED("k_traces");
+            });
+            timed(h, ph.solve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, nullptr); });
+            timed(h, ph.contract, [&] {
+                gt::k_tprod<<<dim3((unsigned)(n * ncols), (unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->dt.p + lo * P * n, (int)n, (int)P,
+                                                                                                        h->As.p, ncols, il, h->Q.p);
+                SL_LAUNCHED("k_tprod");
+                gt::k_hdot<<<dim3((unsigned)(cols * cols * P), (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(
+                    h->As.p, h->Q.p, (int)n, (int)P, cols, (int)n_sets, h->ze.p, il, h->H.p + hsz * lo);
+                SL_LAUNCHED("k_hdot");
+            });
+        }
+        timed(h, ph.d2h, [&] {
+            read_back(h, m, gsz, G_out, sld_out, info_out);
+            SL_CHECK(hipMemcpyAsync(H_out, h->H.p, sizeof(double) * hsz * m, hipMemcpyDeviceToHost, st));
+            SL_CHECK(hipMemcpyAsync(trace_out, h->trace.p, sizeof(double) * m * P, hipMemcpyDeviceToHost, st));
+        });
     });
 }
 
@@ -540,72 +713,8 @@ GT_API int gsum_toep_times(gsum_toep* h, double* ms, int32_t reset) {
 GT_API int gsum_toep_grad(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z, int64_t n_sets,
                           int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out) {
     return guarded([&] {
-        if (!h || !t || !dt || !Z || !G_out || !sld_out || !info_out || !trace_out || !H_out) throw Error("gsum_toep_grad: null pointer argument");
-        if (n_sets < 1) throw Error("gsum_toep_grad: n_sets must be >= 1, got " + std::to_string(n_sets));
-        if (P < 1 || P > 65535) throw Error("gsum_toep_grad: P must be between 1 and 65535, got " + std::to_string(P));
-        check_cols("gsum_toep_grad", cols);
-        check_first_columns("gsum_toep_grad", t, m, n);
-        check_sets("gsum_toep_grad", n, n_sets, cols);
-        if ((int64_t)cols * cols * P > ((int64_t)1 << 31) - 1) throw Error("gsum_toep_grad: cols * cols * P must be < 2^31");
-        const int ncols = (int)(n_sets * cols);
-        const size_t per_theta = (size_t)n * ncols;                            // doubles of Y, and of alpha, per first column
-        const int64_t step = columns_per_launch(m, 2 * per_theta * sizeof(double));
-        const size_t gsz = (size_t)n_sets * cols * cols, hsz = gsz * (size_t)P;
-        run(h, [&] {
-            h->t.reserve((size_t)m * n);
-            h->dt.reserve((size_t)m * P * n);
-            h->Z.reserve(per_theta);
-            h->Y.reserve(per_theta * step);
-            h->As.reserve(per_theta * step);
-            h->W.reserve(4 * per_theta * step);
-            h->Q.reserve(2 * per_theta * step * P);
-            h->steps.reserve((size_t)4 * n * step);
-            h->xd.reserve((size_t)2 * n * step);
-            h->xf.reserve((size_t)n * step);
-            h->sd.reserve((size_t)2 * n * step);
-            h->G.reserve(gsz * m);
-            h->H.reserve(hsz * m);
-            h->trace.reserve((size_t)m * P);
-            h->sld.reserve((size_t)m);
-            h->info.reserve((size_t)m);
-            h->ze.reserve((size_t)ncols);
-            hipStream_t st = h->stream;
-            timed(h, kGH2D, [&] {
-                SL_CHECK(hipMemcpyAsync(h->t.p, t, sizeof(double) * m * n, hipMemcpyHostToDevice, st));
-                SL_CHECK(hipMemcpyAsync(h->dt.p, dt, sizeof(double) * m * P * n, hipMemcpyHostToDevice, st));
-                SL_CHECK(hipMemcpyAsync(h->Z.p, Z, sizeof(double) * per_theta, hipMemcpyHostToDevice, st));
-            });
-            timed(h, kGSchur, [&] { launch_colexp(h, (int)n, ncols); });
-            for (int64_t lo = 0; lo < m; lo += step) {
-                const int64_t cnt = std::min(step, m - lo);
-                const double* tl = h->t.p + lo * n;
-                int32_t* il = h->info.p + lo;
-                timed(h, kGSchur, [&] { launch_schur<true>(h, tl, (int)n, h->Z.p, h->ze.p, ncols, cnt, h->Y.p, h->sld.p + lo, il, h->steps.p); });
-                timed(h, kGLevinson, [&] { launch_levinson(h, tl, (int)n, cnt, h->steps.p, h->xd.p, h->xf.p, h->sld.p + lo, il); });
-                timed(h, kGGram, [&] { launch_gram(h, (int)n, cols, (int)n_sets, cnt, il, h->G.p + gsz * lo); });
-                timed(h, kGDiag, [&] {
-                    gt::k_diagsums<<<dim3((unsigned)n, (unsigned)cnt), gt::kWave, 0, st>>>(h->xd.p, (int)n, il, h->sd.p);
-                    SL_LAUNCHED("k_diagsums");
-                    gt::k_traces<<<dim3((unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->sd.p, h->dt.p + lo * P * n, (int)n, (int)P, il,
-                                                                                         h->trace.p + lo * P);
-                    SL_LAUNCHED("k_traces");
-                });
-                timed(h, kGSolve, [&] { launch_solve(h, (int)n, ncols, cnt, h->xd.p, il, nullptr); });
-                timed(h, kGContract, [&] {
-                    gt::k_tprod<<<dim3((unsigned)(n * ncols), (unsigned)P, (unsigned)cnt), gt::kWave, 0, st>>>(h->dt.p + lo * P * n, (int)n, (int)P,
-                                                                                                            h->As.p, ncols, il, h->Q.p);
-                    SL_LAUNCHED("k_tprod");
-                    gt::k_hdot<<<dim3((unsigned)(cols * cols * P), (unsigned)n_sets, (unsigned)cnt), gt::kWave, 0, st>>>(
-                        h->As.p, h->Q.p, (int)n, (int)P, cols, (int)n_sets, h->ze.p, il, h->H.p + hsz * lo);
-                    SL_LAUNCHED("k_hdot");
-                });
-            }
-            timed(h, kGD2H, [&] {
-                read_back(h, m, gsz, G_out, sld_out, info_out);
-                SL_CHECK(hipMemcpyAsync(H_out, h->H.p, sizeof(double) * hsz * m, hipMemcpyDeviceToHost, st));
-                SL_CHECK(hipMemcpyAsync(trace_out, h->trace.p, sizeof(double) * m * P, hipMemcpyDeviceToHost, st));
-            });
-        });
+        grad_route("gsum_toep_grad", {kGH2D, kGSchur, kGLevinson, kGGram, kGDiag, kGSolve, kGContract, kGD2H}, h, t, m, n, dt, P, Z, n_sets, cols, G_out,
+                   sld_out, info_out, trace_out, H_out);
     });
 }
 
@@ -750,5 +859,38 @@ GT_API int gsum_toep_blocked_times(gsum_toep* h, double* ms, int32_t reset) {
     return guarded([&] {
         if (!h || !ms) throw Error("gsum_toep_blocked_times: null pointer argument");
         read_times(h, kTotalPhases, kGrandPhases - kTotalPhases, ms, reset);
+    });
+}
+
+GT_API int gsum_toep_grad_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z, int64_t n_sets,
+                                  int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out) {
+    return guarded([&] {
+        grad_route("gsum_toep_grad_blocked", {kLH2D, kLUpdate, kLLevinson, kLGram, kLDiagsums, kLSolve, kLContract, kLD2H, &kLevinsonClock}, h, t, m, n, dt,
+                   P, Z, n_sets, cols, G_out, sld_out, info_out, trace_out, H_out);
+    });
+}
+
+GT_API int gsum_toep_solve_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols64, double* x_out,
+                                   double* alpha_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !info_out || (!x_out && !alpha_out) || (alpha_out && !Z)) throw Error("gsum_toep_solve_blocked: null pointer argument");
+        solve_columns("gsum_toep_solve_blocked", {kLH2D, kLUpdate, kLLevinson, kLSolve, kLD2H, &kLevinsonClock}, h, t, m, n, Z, ncols64, x_out, alpha_out,
+                      nullptr, info_out);
+    });
+}
+
+GT_API int gsum_toep_loo_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* p_out,
+                                 double* alpha_out, int32_t* info_out) {
+    return guarded([&] {
+        if (!h || !t || !p_out || !info_out || (alpha_out && !Z)) throw Error("gsum_toep_loo_blocked: null pointer argument");
+        solve_columns("gsum_toep_loo_blocked", {kLH2D, kLUpdate, kLLevinson, kLSolve, kLD2H, &kLevinsonClock}, h, t, m, n, Z, ncols, nullptr, alpha_out,
+                      p_out, info_out);
+    });
+}
+
+GT_API int gsum_toep_levinson_times(gsum_toep* h, double* ms, int32_t reset) {
+    return guarded([&] {
+        if (!h || !ms) throw Error("gsum_toep_levinson_times: null pointer argument");
+        read_times(h, kGrandPhases, kUltimatePhases - kGrandPhases, ms, reset);
     });
 }

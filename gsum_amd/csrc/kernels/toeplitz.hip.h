@@ -31,6 +31,9 @@
 // The blocked route (the comments stand at the kernels): k_schur_lead runs a panel's steps on the rows under the
 //   pivot and hands out their (rho, 1 / c), k_schur_tiles replays them on every row, tile by tile, from one state buffer in HBM
 //   into another, and writes the panel; k_blocked_init forms the state, k_blocked_sld sums the logarithms of the diagonal.
+// The tiled replay (the comments stand at the kernels): k_levinson_tiles replays a panel of (rho, 1 / c) on the
+//   rows of A and B tile by tile, from one state buffer in HBM into another, k_levinson_finish divides by the last pivot and tests x,
+//   k_invdiag_n is k_invdiag with E a runtime number.
 // The step itself is written once, after the double-double functions: step_coeffs (rho, the failure test, 1 / c), rotate, the
 //   generator from t and its state in HBM, a column of L in the panel layout, the tree of sum log L_jj.  Every recursion kernel calls
 //   those, so the routes cannot differ in an expression; the order of their sweeps is their own, and the tests compare them.
@@ -1232,6 +1235,151 @@ __global__ __launch_bounds__(kThreads) void k_blocked_sld(const double* __restri
             if (base + e < n) s += log(d[base + e]);
     }
     sum_log_diag_tree(red, tid, s, bad, sld + theta);
+}
+
+// ---- the tiled replay -------------------------------------------------------------------------------------------
+// Levinson's step is as local as the Schur step: A'[i] and B'[i] need A[i], B[i-1] and the step's (rho, 1 / c), and every (rho, 1 / c)
+// is known before the replay starts (steps, k_coeffs' layout: step k replays row k - 1).  So there is no lead: a panel of kPanelB
+// steps is independent tiles with k_schur_tiles' geometry.  The state lives in HBM, (4, n) doubles per first column (A.h, A.l, B.h,
+// B.l: state_load / state_store with A as u and B as v), twice, both zero-filled before the first panel: the tiles of a panel read
+// one buffer, halo included, and write their own rows to the other.  After step k only the rows 0 .. k are nonzero, so the panel that
+// ends with step k1 launches the tiles 0 .. k1 / kTileR; the rows of a tile that was never launched are the zeros of the fill in both
+// buffers.  Every element goes through rotate in k_levinson's order, so x is k_levinson's bit for bit.
+
+// The steps k0 + 1 .. min(k0 + kPanelB, n - 1) on the rows of tile blockIdx.x, which owns the rows r0 = blockIdx.x * kTileR .. r0 +
+// kTileR - 1 and loads from `cur` the rows from r0 - kPanelB on, kTileE consecutive ones per lane in registers; rows above row 0 and
+// beyond n are zeros.  The first panel (k0 == 0) takes A[0] = B[0] = 1 / sqrt(t_0) (t0_rsqrt) instead of the fill.  B's element that
+// a shift brings over a lane boundary comes by a lane shuffle: no barrier, no LDS.  After s steps the first s rows of the halo are
+// stale; the own rows lie kPanelB below its top and stay exact.  At the end the tile writes its own rows to `nxt`.  A first column
+// with info != 0 is skipped.  grid = (k1 / kTileR + 1, cnt), block = kWave.
+__global__ __launch_bounds__(kWave) void k_levinson_tiles(const double* __restrict__ t, int n, int k0, const double* __restrict__ cur,
+                                                           double* __restrict__ nxt, const double* __restrict__ steps,
+                                                           const int32_t* __restrict__ info) {
+    const int64_t theta = blockIdx.y;
+    if (info[theta] != 0) return;                                             // the same in every lane
+    const int lane = threadIdx.x;
+    const int r0 = (int)blockIdx.x * kTileR;                                  // the tile's first own row
+    const int base = r0 - kPanelB + lane * kTileE;                            // the row of the lane's first element
+    const double* s = cur + theta * 4 * (int64_t)n;
+    double* so = nxt + theta * 4 * (int64_t)n;
+    const double* co = steps + theta * 4 * (int64_t)n;
+    double ah[kTileE], al[kTileE], bh[kTileE], bl[kTileE];
+#pragma unroll
+    for (int e = 0; e < kTileE; ++e) {
+        const int i = base + e;
+        uv g = i >= 0 && i < n ? state_load(s, n, i) : uv{};
+        if (k0 == 0 && i == 0) g.u = g.v = t0_rsqrt(t[theta * n]);
+        ah[e] = g.u.h;
+        al[e] = g.u.l;
+        bh[e] = g.v.h;
+        bl[e] = g.v.l;
+    }
+    const int k1 = min(k0 + kPanelB, n - 1);
+    for (int k = k0 + 1; k <= k1; ++k) {
+        const double* ck = co + 4 * (int64_t)(k - 1);                         // step k replays row k - 1
+        const dd nrho = {-ck[0], -ck[1]}, ic = {ck[2], ck[3]};
+        const double eh = __shfl_up(bh[kTileE - 1], 1, kWave), el = __shfl_up(bl[kTileE - 1], 1, kWave);
+        const dd edge = lane > 0 ? dd{eh, el} : dd{0.0, 0.0};
+#pragma unroll
+        for (int e = kTileE - 1; e >= 0; --e) {
+            const dd bs = e > 0 ? dd{bh[e > 0 ? e - 1 : 0], bl[e > 0 ? e - 1 : 0]} : edge;          // B shifted down by one
+            const uv r = rotate(dd{ah[e], al[e]}, bs, nrho, ic);              // (A, shift(B)) in the roles of (u shifted, v)
+            ah[e] = r.u.h;
+            al[e] = r.u.l;
+            bh[e] = r.v.h;
+            bl[e] = r.v.l;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < kTileE; ++e) {
+        const int i = base + e;
+        if (i >= r0 && i < n) state_store(so, n, i, uv{{ah[e], al[e]}, {bh[e], bl[e]}});
+    }
+}
+
+// x = A / L[n-1, n-1] from the state st the last panel wrote and row n - 1 of steps: xd (m, n, 2) both words, xf (m, n) the fp64
+// rounding, k_levinson's division and its finiteness test.  A first column with info != 0 gives NaN; one whose x is not finite gets
+// info = n + 1, a NaN sld and NaN in its x.  Thread tid takes the rows tid, tid + kThreads, ...  grid = m, block = kThreads.
+__global__ __launch_bounds__(kThreads) void k_levinson_finish(const double* __restrict__ st, int n, const double* __restrict__ steps,
+                                                               double* __restrict__ xd, double* __restrict__ xf, double* __restrict__ sld,
+                                                               int32_t* __restrict__ info) {
+    __shared__ int s_notfinite;                                               // a flag of its own: k_levinson's __syncthreads_or keeps its code
+    const int tid = threadIdx.x;
+    const int64_t theta = blockIdx.x;
+    double* xo = xd + theta * n * 2;
+    double* xr = xf + theta * n;
+    int notfinite = info[theta] != 0 ? 2 : 0;                                 // the same in every thread
+    if (!notfinite) {
+        if (tid == 0) s_notfinite = 0;
+        __syncthreads();
+        const double* s = st + theta * 4 * (int64_t)n;
+        const double* row = steps + (theta * n + (n - 1)) * 4;
+        const dd last = {row[0], row[1]};
+        for (int i = tid; i < n; i += kThreads) {
+            const dd x = dd_div(state_load(s, n, i).u, last);
+            xo[2 * i] = x.h;
+            xo[2 * i + 1] = x.l;
+            xr[i] = x.h;
+            if (!dd_finite(x)) notfinite = 1;
+        }
+        if (notfinite) s_notfinite = 1;                                       // every such thread stores the same word
+        __syncthreads();
+        notfinite = s_notfinite;
+    }
+    if (!notfinite) return;
+    for (int i = tid; i < n; i += kThreads) xo[2 * i] = xo[2 * i + 1] = xr[i] = NAN;
+    if (notfinite == 1 && tid == 0) {
+        info[theta] = n + 1;
+        sld[theta] = NAN;
+    }
+}
+
+// k_invdiag with E a runtime number (the size class of n up to kMaxN, ceil(n / kThreads) beyond, as k_blocked_sld takes it): thread
+// tid sums its E consecutive terms in ascending order, the totals go through the same nine-step scan, and a second pass forms the
+// terms and their running sums again, E being no compile-time array's length, and divides.  For n <= kMaxN this is k_invdiag<E>'s
+// arithmetic in k_invdiag<E>'s order.  grid = m, block = kThreads.
+__global__ __launch_bounds__(kThreads) void k_invdiag_n(const double* __restrict__ xd, int n, int E, const int32_t* __restrict__ info,
+                                                         double* __restrict__ pd) {
+    __shared__ double s_tot[2][kThreads][2];
+    const int tid = threadIdx.x, base = tid * E;
+    const int64_t theta = blockIdx.x;
+    double* p = pd + theta * n;
+    if (info[theta] != 0) {                                                   // the same in every thread
+        for (int e = 0; e < E; ++e)
+            if (base + e < n) p[base + e] = NAN;
+        return;
+    }
+    const double* x = xd + theta * n * 2;
+    const auto term = [&](int r) {
+        const dd a = {x[2 * r], x[2 * r + 1]};
+        const dd b = r > 0 ? dd{x[2 * (n - r)], x[2 * (n - r) + 1]} : dd{0.0, 0.0};
+        return dd_mul(dd_sub(a, b), dd_add(a, b));
+    };
+    dd acc = {0.0, 0.0};
+    for (int e = 0; e < E; ++e)
+        if (base + e < n) acc = dd_add(acc, term(base + e));
+    s_tot[0][tid][0] = acc.h;
+    s_tot[0][tid][1] = acc.l;
+    __syncthreads();
+    int cur = 0;
+    for (int off = 1; off < kThreads; off <<= 1) {                            // inclusive scan of the totals
+        dd s = {s_tot[cur][tid][0], s_tot[cur][tid][1]};
+        if (tid >= off) s = dd_add(dd{s_tot[cur][tid - off][0], s_tot[cur][tid - off][1]}, s);
+        s_tot[cur ^ 1][tid][0] = s.h;
+        s_tot[cur ^ 1][tid][1] = s.l;
+        cur ^= 1;
+        __syncthreads();
+    }
+    const dd before = tid > 0 ? dd{s_tot[cur][tid - 1][0], s_tot[cur][tid - 1][1]} : dd{0.0, 0.0};
+    const dd x0 = {x[0], x[1]};
+    acc = {0.0, 0.0};
+    for (int e = 0; e < E; ++e) {
+        const int r = base + e;
+        if (r < n) {
+            acc = dd_add(acc, term(r));
+            p[r] = dd_div(dd_add(before, acc), x0).h;
+        }
+    }
 }
 
 }  // namespace gt

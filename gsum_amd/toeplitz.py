@@ -22,7 +22,7 @@ import numpy as np
 
 from ._backend import resolve_backend, resolve_device
 from ._lib import FAMILY, GSUM_MAX_RHS, KernelDesc
-from ._toep_lib import check_method
+from ._toep_lib import check_grad_method, check_method
 from .kernels import describe_kernel
 
 __all__ = ["uniform_grid_step", "toeplitz_column", "toeplitz_gram", "toeplitz_max_n", "toeplitz_panel_width", "toeplitz_inverse_column", "toeplitz_solve",
@@ -358,22 +358,28 @@ def _cpu_pieces(t, dt, Z, n_sets, want):
     return G, sld, info, x.astype(float), None if alpha is None else alpha.astype(float), trace, H
 
 
-def toeplitz_inverse_column(t, device=None, backend=None):
+def toeplitz_inverse_column(t, device=None, backend=None, method="columns"):
     """``(x, info)``: the first column ``x = T^-1 e_0`` of the inverse of the symmetric Toeplitz matrices with the first columns t, (n,)
     or (m, n), and ``info`` as ``toeplitz_gram`` gives it, or n + 1 where the recursion went through but x is not finite.  x is NaN where
-    info is not 0.  By Gohberg and Semencul x fixes the whole inverse."""
+    info is not 0.  By Gohberg and Semencul x fixes the whole inverse.  ``method="blocked"``: the blocked
+    route's recursion and Levinson's replay on tiles, bit for bit the default's x, up to ``toeplitz_max_n(method="blocked")``; the
+    same keyword on ``toeplitz_solve``, ``toeplitz_grad``, ``toeplitz_inverse_diagonal`` and ``toeplitz_loo``.  There is no panel
+    route from x on: ``"panel"`` is a ValueError.  ``backend='cpu'`` has one code for both."""
+    check_grad_method(method)
     t2, single = _first_columns(t)
     if resolve_backend(backend) == "cpu":
         _, _, info, x, _, _, _ = _cpu_pieces(t2, None, np.zeros((t2.shape[1], 1)), 1, ())
     else:
         from . import _toep_lib
-        x, _, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, None, want_x=True)
+        x, _, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, None, want_x=True, method=method)
     return (x[0], int(info[0])) if single else (x, info)
 
 
-def toeplitz_solve(t, Z, device=None, backend=None):
+def toeplitz_solve(t, Z, device=None, backend=None, method="columns"):
     """``(alpha, info)``: ``alpha = T^-1 Z`` for the first columns t, (n,) or (m, n), and the right-hand sides Z, (n,) or (n, c): alpha
-    is (n, c) or (m, n, c), NaN where info is not 0.  Four triangular Toeplitz products per column (Gohberg-Semencul), O(n^2 c)."""
+    is (n, c) or (m, n, c), NaN where info is not 0.  Four triangular Toeplitz products per column (Gohberg-Semencul), O(n^2 c).
+    ``method``: see ``toeplitz_inverse_column``."""
+    check_grad_method(method)
     t2, single = _first_columns(t)
     Z = np.asarray(Z, dtype=float)
     if Z.ndim == 1:
@@ -385,16 +391,18 @@ def toeplitz_solve(t, Z, device=None, backend=None):
         _, _, info, _, alpha, _, _ = _cpu_pieces(t2, None, Z, 1, ("alpha",))
     else:
         from . import _toep_lib
-        _, alpha, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, Z, want_x=False)
+        _, alpha, info = _toep_lib.default_handle(resolve_device(device)).solve(t2, Z, want_x=False, method=method)
     return (alpha[0], int(info[0])) if single else (alpha, info)
 
 
-def toeplitz_grad(t, dt, Z, n_sets=1, device=None, backend=None):
+def toeplitz_grad(t, dt, Z, n_sets=1, device=None, backend=None, method="columns"):
     """``(G, sum_log_diag, info, trace, H)``: ``toeplitz_gram``'s three and, for the derivative columns dt, (P, n) or (m, P, n) -- dT_p
     is the symmetric Toeplitz matrix of ``dt[p]`` -- ``trace[p] = tr(T^-1 dT_p)`` and ``H[s, p] = alpha_s^T dT_p alpha_s`` with
     ``alpha_s = T^-1 Z_s`` (exactly symmetric): what ``lml_grad_from_gram`` takes.  Shapes: t (n,) gives trace (P,) and H (n_sets, P, c,
     c); t (m, n) gives (m, P) and (m, n_sets, P, c, c).  Where info is not 0 (n + 1: the inverse's first column is not finite) all
-    outputs are NaN.  G, sum_log_diag and info are bit for bit ``toeplitz_gram``'s."""
+    outputs are NaN.  G, sum_log_diag and info are bit for bit ``toeplitz_gram``'s, with ``method="blocked"`` (see
+    ``toeplitz_inverse_column``) those of ``toeplitz_gram(method="blocked")``."""
+    check_grad_method(method)
     t2, single = _first_columns(t)
     m, n = t2.shape
     dt = np.asarray(dt, dtype=float)
@@ -408,7 +416,7 @@ def toeplitz_grad(t, dt, Z, n_sets=1, device=None, backend=None):
         G, sld, info, _, _, trace, H = _cpu_pieces(t2, dt3, Z, n_sets, ("trace", "H"))
     else:
         from . import _toep_lib
-        G, sld, info, trace, H = _toep_lib.default_handle(resolve_device(device)).grad(t2, dt3, Z, n_sets)
+        G, sld, info, trace, H = _toep_lib.default_handle(resolve_device(device)).grad(t2, dt3, Z, n_sets, method)
     if single:
         return G[0], float(sld[0]), int(info[0]), trace[0], H[0]
     return G, sld, info, trace, H
@@ -544,26 +552,28 @@ def _cpu_inverse_diagonal(t):
     return p, info
 
 
-def toeplitz_inverse_diagonal(t, device=None, backend=None):
+def toeplitz_inverse_diagonal(t, device=None, backend=None, method="columns"):
     """``(p, info)``: ``p = diag(T^-1)`` of the symmetric Toeplitz matrices with the first columns t, (n,) or (m, n), from the inverse's
     first column x by Gohberg and Semencul: ``p_i = (1 / x_0) sum_{r <= i} (x_r^2 - x_{n-r}^2)`` with ``x_n = 0``.  The sums cancel
     heavily on an ill-conditioned T and run in extended precision throughout.  ``info`` as ``toeplitz_inverse_column``; p is NaN where
-    it is not 0."""
+    it is not 0.  ``method``: see ``toeplitz_inverse_column``."""
+    check_grad_method(method)
     t2, single = _first_columns(t)
     if resolve_backend(backend) == "cpu":
         p, info = _cpu_inverse_diagonal(t2)
     else:
         from . import _toep_lib
-        p, _, info = _toep_lib.default_handle(resolve_device(device)).loo(t2, None)
+        p, _, info = _toep_lib.default_handle(resolve_device(device)).loo(t2, None, method)
     return (p[0], int(info[0])) if single else (p, info)
 
 
-def toeplitz_loo(t, y, mean=0.0, device=None, backend=None):
+def toeplitz_loo(t, y, mean=0.0, device=None, backend=None, method="columns"):
     """The ``LooResult`` (``gsum_amd.loo``) of the curves y, (n,) or (n, n_curves), under N(mean, T), T the symmetric Toeplitz matrix
     with the first column t, (n,): ``LooFactor.loo``'s formulas with ``a = T^-1 (y - mean)`` (``toeplitz_solve``) and ``p = diag(T^-1)``
     (``toeplitz_inverse_diagonal``), both from one recursion; nothing n x n is formed.  ``mean`` is a scalar or (n,).
-    numpy.linalg.LinAlgError where T is not positive definite."""
+    numpy.linalg.LinAlgError where T is not positive definite.  ``method``: see ``toeplitz_inverse_column``."""
     from .loo import LooResult
+    check_grad_method(method)
     t = np.asarray(t, dtype=float)
     if t.ndim != 1 or t.size < 1:
         raise ValueError(f"t must have shape (n,), got {t.shape}")
@@ -580,7 +590,7 @@ def toeplitz_loo(t, y, mean=0.0, device=None, backend=None):
         _, _, _, _, a, _, _ = _cpu_pieces(t[None], None, r, 1, ("alpha",))
     else:
         from . import _toep_lib
-        p, a, info = _toep_lib.default_handle(resolve_device(device)).loo(t[None], r)
+        p, a, info = _toep_lib.default_handle(resolve_device(device)).loo(t[None], r, method)
     if info[0] != 0:
         raise np.linalg.LinAlgError("Matrix is not positive definite")
     p, a = p[0], a[0].reshape(y.shape)

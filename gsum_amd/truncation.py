@@ -110,9 +110,10 @@ class TruncationGP:
         return y_mean, np.sqrt(self._cov_diag(X, start=order + 1))
 
     # -- fit (models.py:1367-1387) -------------------------------------------------------------------
-    def fit(self, X, y, orders, dX=None, dy=None, structure=None):
+    def fit(self, X, y, orders, dX=None, dy=None, structure=None, toeplitz_grad_method="columns"):
         """``structure="toeplitz"``: the calibration of the coefficients' process runs on the structured route
-        (``ConjugateGaussianProcess.fit``); everything after it stays dense."""
+        (``ConjugateGaussianProcess.fit``); everything after it stays dense.  ``toeplitz_grad_method``: that fit's, read with
+        ``structure="toeplitz"`` alone; the final factorisation and ``predict`` are dense whatever it says."""
         for name, fn in (("ratio", lambda: self.ratio(X, **self.ratio_kws)), ("ref", lambda: self.ref(X))):
             if np.atleast_1d(fn()).ndim > 1:
                 raise ValueError(f'{name} must return a 1d array or a scalar')            # models.py:1379-1382
@@ -121,7 +122,7 @@ class TruncationGP:
         if structure is None:
             self.coeffs_process.fit(X=X, y=self.coeffs_)
         else:
-            self.coeffs_process.fit(X=X, y=self.coeffs_, structure=structure)
+            self.coeffs_process.fit(X=X, y=self.coeffs_, structure=structure, toeplitz_grad_method=toeplitz_grad_method)
         self._fit = True
         return self
 

@@ -137,6 +137,32 @@
  *   the formation of the state and the sum of the logarithms), 3 the triangular blocks, 4 the trailing updates (with the scaling of
  *   the right-hand sides), 5 the sums G, quad and cross, 6 cov, 7 device-to-host copies.  The other four clocks are not charged by
  *   them.
+ *
+ * The tiled replay (opt-in; the entry points above are unchanged, and gsum_toep_grad, gsum_toep_solve and gsum_toep_loo keep refusing
+ * n > gsum_toep_max_n).  Their replay of Levinson's recursion keeps A and B of a whole first column in one workgroup.  Its step is as
+ * local as the Schur step -- A'[i] and B'[i] need A[i], B[i-1] and the step's (rho, 1 / c) -- and every (rho, 1 / c) is known before it
+ * starts, so a panel of B steps is independent tiles of R rows with a halo of B rows above them: one wave each, A and B in device
+ * memory, two zero-filled buffers of 4 n doubles per first column, read from one and written to the other.  After step k only the
+ * rows 0 .. k are nonzero, so a panel launches the tiles up to its last step's.  The coefficients are those of the blocked route,
+ * whose lead overwrites them panel after panel: the entry points below keep them (4 n doubles per first column, row n - 1 both words
+ * of L[n-1, n-1]).  Every element sees the expressions of the entry points above in their order: for n <= gsum_toep_max_n x, alpha,
+ * p, trace, H, sum_log_diag and info are bit for bit those of gsum_toep_grad, gsum_toep_solve and gsum_toep_loo, and G that of
+ * gsum_toep_gram_blocked.  The limit is gsum_toep_blocked_max_n: the kernels from x on index in 64 bits wherever a product with n or
+ * the number of columns occurs, and their grids are covered by n * n_sets * cols < 2^31.  Their cost stays O(n^2) per column.
+ *
+ * gsum_toep_grad_blocked: the arguments, outputs and refusals of gsum_toep_grad, with n <= gsum_toep_blocked_max_n.  The first columns
+ *   go through in chunks that keep what gsum_toep_gram_blocked keeps and the coefficients, the two states, x, the diagonal sums and
+ *   (5 + 2 P) doubles per entry of Z within 1 GiB.
+ *
+ * gsum_toep_solve_blocked, gsum_toep_loo_blocked: the arguments, outputs and refusals of gsum_toep_solve and gsum_toep_loo, with the
+ *   same limit.  The recursion runs without right-hand sides.  diag(T^-1) is summed in gsum_toep_loo's order, which for n >
+ *   gsum_toep_max_n continues as ceil(n / 512) consecutive terms per thread of 512, then the scan: fixed by n alone.
+ *
+ * gsum_toep_levinson_times: ms[0..10] = device milliseconds spent by the three in: 0 host-to-device copies, 1 the leads (with the
+ *   copies that keep their coefficients), 2 the Schur tiles, 3 the triangular blocks, 4 the trailing updates (with the scaling of
+ *   the right-hand sides), 5 the tiled replay, 6 the Gram matrices, 7 the diagonal sums and traces, 8 the inverse's diagonal and the
+ *   Gohberg-Semencul products, 9 the Toeplitz products and contractions of H, 10 device-to-host copies.  The other five clocks are
+ *   not charged by them, nor this one by the other entry points.
  */
 #ifndef GSUM_TOEP_H
 #define GSUM_TOEP_H
@@ -182,6 +208,13 @@ int gsum_toep_gram_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, 
 int gsum_toep_predict_blocked(gsum_toep* h, const double* t, int64_t n, const double* K, int64_t q, const double* Z, int32_t c, double* quad_out,
                               double* cross_out, double* cov_out, double* G_out, double* sld_out, int32_t* info_out);
 int gsum_toep_blocked_times(gsum_toep* h, double* ms, int32_t reset);
+int gsum_toep_grad_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* dt, int64_t P, const double* Z, int64_t n_sets,
+                           int32_t cols, double* G_out, double* sld_out, int32_t* info_out, double* trace_out, double* H_out);
+int gsum_toep_solve_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* x_out,
+                            double* alpha_out, int32_t* info_out);
+int gsum_toep_loo_blocked(gsum_toep* h, const double* t, int64_t m, int64_t n, const double* Z, int64_t ncols, double* p_out, double* alpha_out,
+                          int32_t* info_out);
+int gsum_toep_levinson_times(gsum_toep* h, double* ms, int32_t reset);
 
 #ifdef __cplusplus
 }
