@@ -56,7 +56,9 @@ def _tree_matrix(desc, X, Y, param=None):
         if op >= OP_POW:                       # Exponentiation (kernels.py: K ** exponent, K_gradient *= exponent K ** (exponent - 1))
             e = desc.cval[op - OP_POW]
             a, da = stack.pop()
-            stack.append((a ** e, da * (e * a ** (e - 1))))
+            # (``zero`` itself marks an operand that does not hold the parameter: scikit-learn has no K_gradient column for it there, and
+            # 0 * inf on an underflowed base must not turn its exact zeros into NaN)
+            stack.append((a ** e, zero if da is zero else da * (e * a ** (e - 1))))
         elif op >= OP_WHITE:
             c = op - OP_WHITE
             hit = param is not None and param.code == GradParam.TREE_WHITE and param.dim == c
@@ -82,7 +84,10 @@ def _tree_matrix(desc, X, Y, param=None):
                 stack.append((_leaf(desc.leaf[l], X.shape[1])(X, Yv), zero))
         else:
             (b, db), (a, da) = stack.pop(), stack.pop()
-            stack.append((a + b, da + db) if op == OP_ADD else (a * b, da * b + a * db))
+            if da is zero and db is zero:
+                stack.append((a + b if op == OP_ADD else a * b, zero))
+            else:
+                stack.append((a + b, da + db) if op == OP_ADD else (a * b, da * b + a * db))
     return stack[0]
 
 
@@ -391,30 +396,39 @@ class CpuContext:
         G, sld, info, M = self._evaluate(desc, X, rhs, nugget)
         if info:
             return G, sld, info, np.zeros(P), np.zeros((P, k, k))
-        n, d = X.shape
+        n = X.shape[0]
         V = _cho_solve((M.A, True), rhs)
         Rinv = _cho_solve((M.A, True), np.eye(n))
+        trace, H = np.empty(P), np.empty((P, k, k))
+        for p, dR in enumerate(self.grad_entries(desc, params, X)):
+            trace[p] = np.einsum("ij,ji->", Rinv, dR)
+            H[p] = V.T @ dR @ V
+        return G, sld, 0, trace, H
+
+    def grad_entries(self, desc, params, X, rhs=None, nugget=0.0):
+        """(P, n, n): dR_p = d kernel(X) / d log theta_p, scikit-learn evaluating the leaves -- the matrices ``lml_grad`` contracts (the
+        device's are read out by ``HipContext.grad_entries`` of the lab build; ``rhs`` and ``nugget`` are taken for its signature only)."""
+        X = np.asarray(X, dtype=float)
+        n, d = X.shape
         dK = None
         if desc.n_ops == 0:
             term = ConstantKernel(float(desc.amplitude), constant_value_bounds=(1e-300, 1e300)) * _leaf(desc, d, free=True)
             _, dK = term(X, eval_gradient=True)              # [:, :, 0]: d / d log amplitude; [:, :, 1:]: length scale(s)
-        trace, H = np.empty(P), np.empty((P, k, k))
+        out = np.empty((len(params), n, n))
         for p, pr in enumerate(params):
             if pr.code >= GradParam.TREE_CONST:
-                dR = _tree_matrix(desc, X, None, pr)[1]
+                out[p] = _tree_matrix(desc, X, None, pr)[1]
             elif pr.code == GradParam.AMPLITUDE:
-                dR = dK[:, :, 0]
+                out[p] = dK[:, :, 0]
             elif pr.code == GradParam.LENGTH_ISO:
-                dR = dK[:, :, 1]
+                out[p] = dK[:, :, 1]
             elif pr.code == GradParam.LENGTH_DIM:
-                dR = dK[:, :, 1 + pr.dim]
+                out[p] = dK[:, :, 1 + pr.dim]
             elif pr.code == GradParam.WHITE:
-                dR = pr.weight * np.eye(n)
+                out[p] = pr.weight * np.eye(n)
             else:
-                dR = np.full((n, n), pr.weight)
-            trace[p] = np.einsum("ij,ji->", Rinv, dR)
-            H[p] = V.T @ dR @ V
-        return G, sld, 0, trace, H
+                out[p] = np.full((n, n), pr.weight)
+        return out
 
     def lml_grad_batch(self, descs, params, X, rhs, nugget):
         out = [self.lml_grad(d, p, X, rhs, nugget) for d, p in zip(descs, params)]

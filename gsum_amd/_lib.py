@@ -229,6 +229,7 @@ LAB_PROTOTYPES = {
     "gsum_debug_pipe_probe": (C.c_int, [_p, C.c_int32, C.POINTER(C.c_int32)]),
     "gsum_debug_diag_stamps": (C.c_int, [_p, _ip]),
     "gsum_debug_wave_factor": (C.c_int, [_p, C.c_int32, _dp, _ip]),
+    "gsum_debug_grad_entries": (C.c_int, [_p, C.c_int32, _dp, C.c_int64]),
     "gsum_debug_chain_stamps": (C.c_int, [_p, _dp, C.c_int32, C.POINTER(C.c_int32)]),
     "gsum_probe_mfma_f64": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "gsum_probe_hbm_write": (C.c_int, [_p, C.c_int64, _dp]),
@@ -794,6 +795,21 @@ class HipContext:
         self._check(self._lib.gsum_debug_wave_factor(self._h, int(eval_index), None, order.ctypes.data_as(_ip)))
         out = np.empty((int(order[0]), int(order[0])))
         self._check(self._lib.gsum_debug_wave_factor(self._h, int(eval_index), _ptr(out), order.ctypes.data_as(_ip)))
+        return out
+
+    def grad_entries(self, desc: KernelDesc, params, X, rhs, nugget: float) -> np.ndarray:
+        """(P, n, n): the entries of dR_p = d kernel(X) / d log theta_p as the production kernels of :meth:`lml_grad` computed them (lab build,
+        gsum_debug_grad_entries).  One ``lml_grad`` per parameter, with ``[params[p]]`` alone: the one-workgroup path (n <= 128) keeps its last
+        parameter's square only.  The general path stores lower triangles; they are mirrored here."""
+        n = _f64(X).shape[0]
+        out = np.empty((len(params), n, n))
+        for p, pr in enumerate(params):
+            info = self.lml_grad(desc, [pr], X, rhs, nugget)[2]
+            if info != 0:
+                raise RuntimeError(f"grad_entries: the evaluation failed (info = {info})")
+            self._check(self._lib.gsum_debug_grad_entries(self._h, 0, _ptr(out[p]), n))
+            if n > 128 or not self.get_option("small_path"):
+                out[p] = np.tril(out[p]) + np.tril(out[p], -1).T
         return out
 
     PROFILE_CLASSES = ("kernel_build", "diag_block", "panel_gemm", "bulk_update", "other")

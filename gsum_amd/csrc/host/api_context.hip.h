@@ -311,7 +311,10 @@ int gsum_set_option(gsum_ctx* ctx, const char* name, int64_t value) {
         if (ctx->pscratch) GS_CHECK(hipFree(ctx->pscratch));
         ctx->scratch = ctx->gws = ctx->pscratch = nullptr;
         ctx->scratch_cap = ctx->gws_cap = ctx->pscratch_cap = 0;
-        gs_wave_release(ctx, false);                           // the groups' workspaces (their streams stay)
+#ifdef GSUM_LAB
+        ctx->grad_left.kind = 0;
+#endif
+        gs_wave_release(ctx, false);                          // the groups' workspaces (their streams stay)
         for (int i = 0; i < ctx->n_slots_ready; ++i) {         // and the per-slot workspace matrices of the fused path
             gs_mat_release(ctx->slots[i].ws);
             ctx->slots[i].ws = nullptr;

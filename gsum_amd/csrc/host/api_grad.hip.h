@@ -268,6 +268,14 @@ static int gs_grad_post(gsum_ctx* ctx, gs_slot* sl, gsum_mat* m, const gsum_kern
     hipLaunchKernelGGL(k_grad_reduce2, dim3((unsigned)P), dim3(256), 0, s, part, chunks, dout);
     GS_CHECK(hipGetLastError());
     GS_CHECK(hipMemcpyAsync(sl->hgrad, dout, (size_t)P * GS_GRES_LEN * 8, hipMemcpyDeviceToHost, s));
+#ifdef GSUM_LAB
+    if (split && ctx->grad_left_ok && sl == &ctx->slots[0]) {           // the stored triangles of k_grad_contract<*, *, true>
+        auto& g = ctx->grad_left;
+        g.kind = 1; g.P = P; g.base = sl->gws; g.off = (size_t)(r->dR - sl->gws);
+        g.n = n; g.ld = ldg; g.stride = r->dr_stride;
+        g.need = (g.off + (size_t)P * (size_t)r->dr_stride) * 8;
+    }
+#endif
     return 0;
 }
 
@@ -327,6 +335,14 @@ static int gs_grad_small(gsum_ctx* ctx, const gsum_kernel_desc* descs, int n_des
                 gs_unpack_grad(hg + ((size_t)e * P + p) * GS_GRES_LEN, info_out[i] == 0, k, P, i, p, H_out, trace_out);
         }
     }
+#ifdef GSUM_LAB
+    if (n_desc == 1 && ctx->grad_left_ok) {                            // dRm of the last parameter: slot A of evaluation 0 (k_grad_small)
+        auto& g = ctx->grad_left;
+        g.kind = 2; g.P = P; g.base = ctx->scratch; g.off = o_scr / 8;
+        g.n = ctx->in->n; g.ld = 128; g.stride = 0;
+        g.need = o_scr + (size_t)GS_GSMALL_SCRATCH * 8;
+    }
+#endif
     return 0;
 }
 
@@ -357,8 +373,16 @@ int gsum_lml_grad(gsum_ctx* ctx, const gsum_kernel_desc* desc, const gsum_grad_p
     if (rc) return rc;
     ctx->in = &ctx->op;
     if (gs_check_desc(ctx, desc, d)) return -2;
-    if (n <= GS_GSMALL_MAX && ctx->small_path) return gs_grad_small(ctx, desc, 1, params, n_params, nugget, G_out, sld_out, info_out, trace_out, H_out);
-    return gs_grad_single(ctx, desc, params, n_params, nugget, G_out, sld_out, info_out, trace_out, H_out);
+#ifdef GSUM_LAB
+    ctx->grad_left_ok = true;               // (this call alone may leave its kernel-gradient entries to gsum_debug_grad_entries)
+#endif
+    if (n <= GS_GSMALL_MAX && ctx->small_path) rc = gs_grad_small(ctx, desc, 1, params, n_params, nugget, G_out, sld_out, info_out, trace_out, H_out);
+    else rc = gs_grad_single(ctx, desc, params, n_params, nugget, G_out, sld_out, info_out, trace_out, H_out);
+#ifdef GSUM_LAB
+    ctx->grad_left_ok = false;
+    if (rc || info_out[0] != 0) ctx->grad_left.kind = 0;      // (a failed factorisation ends k_grad_small before its contractions)
+#endif
+    return rc;
 }
 
 // A batch of value + gradient evaluations on the GROUPED schedule (round 4): the factorisations of up to wave_groups x wave_size kernels

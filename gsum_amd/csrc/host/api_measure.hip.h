@@ -87,6 +87,36 @@ int gsum_debug_wave_factor(gsum_ctx* ctx, int32_t eval, double* out, int64_t* or
     GS_FAIL("gsum_debug_wave_factor: no group workspace holds that evaluation");
 }
 
+// The entries of dR_p the production kernels of the last gsum_lml_grad computed (ctx->grad_left, written by gs_grad_post / gs_grad_small):
+// out is n x n, row-major.  General path: the stored lower triangle of k_grad_contract<*, *, true>, zeros above the diagonal; one-workgroup path:
+// the whole square k_grad_small left, for its last parameter only.
+int gsum_debug_grad_entries(gsum_ctx* ctx, int32_t p, double* out, int64_t n) {
+    if (!ctx || !out) return -2;
+    const auto& g = ctx->grad_left;
+    if (!g.kind)
+        GS_FAIL("gsum_debug_grad_entries: nothing to read -- the last call was not a single successful gsum_lml_grad, it ran with grad_split = 0, "
+                "or its workspace was released or used again since");
+    const double* base = g.kind == 1 ? ctx->slots[0].gws : ctx->scratch;
+    const size_t cap = g.kind == 1 ? ctx->slots[0].gws_cap : ctx->scratch_cap;
+    if (!base || base != g.base || cap < g.need) GS_FAIL("gsum_debug_grad_entries: the workspace of that evaluation is gone");
+    if (n != g.n) GS_FAIL("gsum_debug_grad_entries: the last gsum_lml_grad had another order");
+    if (p < 0 || p >= g.P) GS_FAIL("gsum_debug_grad_entries: parameter index out of range");
+    if (g.kind == 2 && p != g.P - 1) GS_FAIL("gsum_debug_grad_entries: the one-workgroup path keeps the entries of its LAST parameter only (n <= 128)");
+    GS_CHECK(hipSetDevice(ctx->device));
+    GS_CHECK(hipDeviceSynchronize());
+    const double* src = base + g.off + (size_t)p * (size_t)g.stride;
+    if (g.kind == 2) {
+        GS_CHECK(hipMemcpy2D(out, (size_t)n * sizeof(double), src, (size_t)g.ld * sizeof(double), (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    // (above the diagonal the workspace holds whatever it held: staged here, never handed out)
+    std::vector<double> rows((size_t)n * (size_t)n);
+    GS_CHECK(hipMemcpy2D(rows.data(), (size_t)n * sizeof(double), src, (size_t)g.ld * sizeof(double), (size_t)n * sizeof(double), (size_t)n, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < n; ++j) out[i * n + j] = j <= i ? rows[(size_t)(i * n + j)] : 0.0;
+    return 0;
+}
+
 #endif  // GSUM_LAB
 
 int gsum_kernel_profile(gsum_ctx* ctx, double* ms5, double* flops5, int64_t* launches5) {

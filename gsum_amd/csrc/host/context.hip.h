@@ -202,6 +202,20 @@ struct gsum_ctx {
     double* pscratch = nullptr; size_t pscratch_cap = 0;    // pivoted Cholesky: two trailing-matrix buffers, the panel, its bookkeeping
     double* hbatch = nullptr; size_t hbatch_cap = 0;   // pinned host buffer for the fused paths' result records
     double* gws = nullptr; size_t gws_cap = 0;     // gradient path: U = L^-T, R^-1, V^T, per-parameter partials
+#ifdef GSUM_LAB
+    // lab (gsum_debug_grad_entries): where the last gsum_lml_grad left the kernel-gradient entries its kernels computed.  kind 0: nowhere;
+    // 1: P stored lower triangles in slot 0's gradient workspace (the split contraction); 2: the last parameter's n x n square in the
+    // one-workgroup scratch of evaluation 0.  gs_reserve and "release_scratch" clear the record, so it never outlives the memory it names.
+    // RULE this rests on: every writer of `scratch` or of a slot's `gws` calls gs_reserve on that buffer first (all of them do today); code
+    // that writes either buffer without reserving it must clear `grad_left.kind` itself.
+    struct {
+        int kind = 0, P = 0;
+        const double* base = nullptr;          // the buffer (slots[0].gws | scratch) as it was when the entries were written
+        size_t off = 0, need = 0;              // parameter 0's first entry (doubles from base); bytes of the buffer the entries end at
+        int64_t n = 0, ld = 0, stride = 0;     // order, leading dimension, doubles between two parameters
+    } grad_left;
+    bool grad_left_ok = false;                 // set inside gsum_lml_grad only: a batch call leaves nothing to read
+#endif
     double timers[4] = {0, 0, 0, 0};
     unsigned long long* dstamps = nullptr;   // 8 u64: phase stamps of the last diagonal-block kernel
     int diag_stamps = 0;
@@ -312,6 +326,9 @@ static int gs_need_factor(gsum_ctx* ctx, const gsum_mat* m, const char* call) {
 }
 
 static int gs_reserve(gsum_ctx* ctx, double** p, size_t* cap, size_t bytes) {
+#ifdef GSUM_LAB
+    ctx->grad_left.kind = 0;        // whoever reserves a work buffer is about to write it
+#endif
     if (*cap >= bytes && *p) return 0;
     if (*p) GS_CHECK(hipFree(*p));
     *p = nullptr;

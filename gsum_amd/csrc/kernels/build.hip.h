@@ -383,7 +383,12 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
 // Sum / Product / Exponentiation tree over stationary leaves (RBF, Matern 1/2 3/2 5/2 inf, RationalQuadratic, ExpSineSquared), ConstantKernel and WhiteKernel is
 // evaluated entry by entry as a postfix program in scikit-learn's own evaluation order (Sum: k1 + k2, kernels.py:858-866;
 // Product: k1 * k2, :956-966), so that `RBF + RBF` or `C * RBF + C * Matern` come out bit-identical to sklearn's matrix like
-// the flattened family does; RationalQuadratic goes through pow() and is within an ulp or two of numpy's.
+// the flattened family does -- sums and products over RBF and Matern (1/2, 3/2, 5/2, inf) leaves, where the exponential is the
+// table algorithm's or exactly zero; a RationalQuadratic leaf goes through pow() and is within an ulp or two of numpy's (measured: one).
+// Both are asserted entry by entry, one- and two-argument form, by tests/test_gpu_kernel_entries.py.  No bits are claimed for DotProduct
+// (the inner product is summed in index order here, in BLAS's order by numpy: ulps apart wherever the partial sums round), for ExpSineSquared
+// (the device library's sin against numpy's: 3 ulps at (1, 3), 15 at (0.5, 0.75) on the test's lattice), for Exponentiation (pow() where numpy
+// squares or takes a root: one ulp on up to a fifth of the entries) or for the subnormal band above: those entries are held to long-double truth instead.
 // The same walk with dual numbers gives d kernel / d log(parameter) for the gradient path (sklearn's K_gradient formulas per leaf:
 // RBF :1567-1577, Matern :1740-1771, RationalQuadratic :1893-1901; product and sum rules for the operators).
 #define GS_TREE_STACK 8
@@ -477,23 +482,31 @@ __device__ __forceinline__ double gs_tree_eval(const gsum_kernel_desc& t, const 
 #pragma clang fp contract(off)
     double sv[GS_TREE_STACK], sd[GS_TREE_STACK];
     int sp = 0;
+    // bit i: the sub-tree in stack slot i holds the parameter.  scikit-learn's K_gradient has a column for a parameter only in the operand that
+    // owns it: an Exponentiation scales the derivatives of ITS parameters (0 * inf = NaN where its base underflowed and the exponent is below 1,
+    // like numpy) and has no say in the others', whose exact 0 must not meet that inf (tests/test_gpu_kernel_entries.py)
+    unsigned has = 0;
     const int code = pr ? pr->code : -1, pdim = pr ? pr->dim : 0;
     for (int k = 0; k < t.n_ops; ++k) {
         const int op = t.op[k];
         if (op >= GSUM_OP_POW) {                  // Exponentiation: K ** exponent, K_gradient *= exponent K ** (exponent - 1)
             const double e = t.cval[op - GSUM_OP_POW], a = sv[sp - 1];
             sv[sp - 1] = pow(a, e);
-            sd[sp - 1] = sd[sp - 1] * (e * pow(a, e - 1.0));
+            if ((has >> (sp - 1)) & 1u) sd[sp - 1] = sd[sp - 1] * (e * pow(a, e - 1.0));
         } else if (op >= GSUM_OP_WHITE) {
             const int c = op - GSUM_OP_WHITE;
             const double w = diag ? t.cval[c] : 0.0;
+            const bool mine = code == GSUM_GRAD_TREE_WHITE && pdim == c;
             sv[sp] = w;
-            sd[sp] = (code == GSUM_GRAD_TREE_WHITE && pdim == c) ? w : 0.0;
+            sd[sp] = mine ? w : 0.0;
+            has = (has & ~(1u << sp)) | ((unsigned)mine << sp);
             ++sp;
         } else if (op >= GSUM_OP_CONST) {
             const int c = op - GSUM_OP_CONST;
+            const bool mine = code == GSUM_GRAD_TREE_CONST && pdim == c;
             sv[sp] = t.cval[c];
-            sd[sp] = (code == GSUM_GRAD_TREE_CONST && pdim == c) ? t.cval[c] : 0.0;
+            sd[sp] = mine ? t.cval[c] : 0.0;
+            has = (has & ~(1u << sp)) | ((unsigned)mine << sp);
             ++sp;
         } else if (op >= GSUM_OP_LEAF) {
             const int l = op - GSUM_OP_LEAF;
@@ -504,9 +517,11 @@ __device__ __forceinline__ double gs_tree_eval(const gsum_kernel_desc& t, const 
             gs_leaf_eval(t.leaf[l], xi, xj, d, diag, want, pdim & 15, v, dv, cross);
             sv[sp] = v;
             sd[sp] = dv;
+            has = (has & ~(1u << sp)) | ((unsigned)(want != 0) << sp);
             ++sp;
         } else {
             const double b = sv[sp - 1], db = sd[sp - 1], a = sv[sp - 2], da = sd[sp - 2];
+            const unsigned h = ((has >> (sp - 1)) | (has >> (sp - 2))) & 1u;
             sp -= 2;
             if (op == GSUM_OP_ADD) {
                 sv[sp] = a + b;
@@ -515,6 +530,7 @@ __device__ __forceinline__ double gs_tree_eval(const gsum_kernel_desc& t, const 
                 sv[sp] = a * b;
                 sd[sp] = da * b + a * db;
             }
+            has = (has & ~(1u << sp)) | (h << sp);
             ++sp;
         }
     }

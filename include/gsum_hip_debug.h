@@ -31,6 +31,13 @@ int gsum_debug_diag_stamps(gsum_ctx* ctx, int64_t* out64);
 /* the augmented workspace matrix ((np + 16)^2 doubles, row-major; lower triangle = the factor, the right-hand-side rows below it) that the
  * last grouped batch call left for its evaluation `eval` -- what gsum_lml_grad_batch reads.  *order = np + 16; out == NULL: the order only. */
 int gsum_debug_wave_factor(gsum_ctx* ctx, int32_t eval, double* out, int64_t* order);
+/* the entries of dR_p = d kernel(X) / d log theta_p that the production kernels of the last single gsum_lml_grad (order n, P parameters) computed
+ * and left on the device; out: n x n doubles, row-major.  General path (n >= 129, or "small_path" = 0; "grad_split" = 1, the default): the lower
+ * triangle k_grad_contract<*, *, true> stored in the slot's gradient workspace, zeros above the diagonal, any p.  One-workgroup path (n <= 128):
+ * the whole square k_grad_small left in evaluation 0's scratch, which is that of its LAST parameter: p == P - 1 only (call gsum_lml_grad with one
+ * parameter at a time).  Refuses with a message (-2) instead of reading memory the evaluation no longer owns: after "release_scratch", after any
+ * call that reserved a work buffer since, after a batch call or a failed evaluation, with "grad_split" = 0, for another order or parameter. */
+int gsum_debug_grad_entries(gsum_ctx* ctx, int32_t p, double* out, int64_t n);
 /* the pairwise stream probe of gsum_init (option "pipes_ok") on the context's four streams plus `extra` (0..4) streams created for the
  * call: out = (4 + extra)^2 overlaps of the pairs' two 100-us kernels in 1/1000 of their length (diagonal 1000).  A pair on one
  * command-processor pipe takes turns (~0); DESIGN.md section 4.1. */
