@@ -818,13 +818,19 @@ class HipContext:
         """Per kernel class {name: dict(ms, flops, launches)} of the launches profiled since the last read-out (option
         "profile_gemm" = N: every launch of every N-th fused evaluation); resets the record.  ``bulk_update`` also carries ``tiles`` and
         ``tiles_run``: the far-update tiles the profiled batch calls launched and how many of them had something to subtract (option
-        "wave_skip_zero": a tile whose operand panels are exactly zero returns at once).  ``flops`` stays the dense algorithmic count."""
+        "wave_skip_zero": a tile whose operand panels are exactly zero returns at once).  ``flops`` stays the dense algorithmic count.
+        ``panel_gemm`` carries ``panel_groups`` and ``panel_groups_loaded``: the 16-row groups (waves) the batch calls' panel solves
+        launched and how many of them went on to load their rows (option "wave_env": a group the kernel build left all zero up to
+        the panel returns first); ``bulk_update["tiles_listed"]`` is the sum of the far updates' live-tile counts (option
+        "wave_far_plan"; 0 with the option off)."""
         ms, fl, cnt = np.zeros(5), np.zeros(5), np.zeros(5, dtype=np.int64)
-        tiles, tiles_run = (int(self._lib.gsum_get_option(self._h, k)) for k in (b"bulk_tiles", b"bulk_tiles_run"))
+        tiles, tiles_run, listed, groups, loaded = (int(self._lib.gsum_get_option(self._h, k)) for k in
+                                                    (b"bulk_tiles", b"bulk_tiles_run", b"bulk_tiles_listed", b"panel_groups", b"panel_groups_loaded"))
         self._check(self._lib.gsum_kernel_profile(self._h, _ptr(ms), _ptr(fl), cnt.ctypes.data_as(_ip)))
         prof = {name: dict(ms=float(ms[i]), flops=float(fl[i]), launches=int(cnt[i]))
                 for i, name in enumerate(self.PROFILE_CLASSES)}
-        prof["bulk_update"].update(tiles=tiles, tiles_run=tiles_run)
+        prof["bulk_update"].update(tiles=tiles, tiles_run=tiles_run, tiles_listed=listed)
+        prof["panel_gemm"].update(panel_groups=groups, panel_groups_loaded=loaded)
         return prof
 
     def pipe_probe(self, extra: int = 0) -> np.ndarray:

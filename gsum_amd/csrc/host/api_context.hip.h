@@ -176,12 +176,16 @@ int64_t gsum_get_option(gsum_ctx* ctx, const char* name) {
     if (!strcmp(name, "wave_groups")) return ctx->wave_groups;
     if (!strcmp(name, "wave_size")) return ctx->wave_size;
     if (!strcmp(name, "wave_skip_zero")) return ctx->wave_skip_zero;
+    if (!strcmp(name, "wave_env")) return ctx->wave_env;
+    if (!strcmp(name, "wave_far_plan")) return ctx->wave_far_plan;
     if (!strcmp(name, "bulk_tiles")) return ctx->prof_tiles;                 // far-update tiles of the profiled batch calls: launched ...
-    if (!strcmp(name, "bulk_tiles_run")) {                                  // ... and with something to subtract (synchronises)
-        unsigned h = 0;
+    if (!strcmp(name, "panel_groups")) return ctx->prof_panel_groups;       // ... their panel-solve waves (16-row groups): launched ...
+    if (!strcmp(name, "bulk_tiles_run") || !strcmp(name, "panel_groups_loaded") || !strcmp(name, "bulk_tiles_listed")) {
+        unsigned h = 0;               // ... and tiles with something to subtract / waves that loaded their rows / tiles the far plans listed (synchronises)
+        const int slot = name[0] == 'p' ? 1 : (!strcmp(name, "bulk_tiles_listed") ? 2 : 0);
         if (!ctx->prof_tiles_run) return 0;
         if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-            hipMemcpy(&h, ctx->prof_tiles_run, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+            hipMemcpy(&h, ctx->prof_tiles_run + slot, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return -1;
         return (int64_t)h;
     }
     if (!strcmp(name, "lookahead")) return ctx->lookahead;
@@ -336,6 +340,8 @@ int gsum_set_option(gsum_ctx* ctx, const char* name, int64_t value) {
     else if (!strcmp(name, "wave_groups")) ctx->wave_groups = (int)std::max<int64_t>(1, std::min<int64_t>(GS_WV_STREAM_GROUPS, value));
     else if (!strcmp(name, "wave_size")) ctx->wave_size = (int)std::max<int64_t>(1, std::min<int64_t>(GS_WVC_MAX, value));
     else if (!strcmp(name, "wave_skip_zero")) ctx->wave_skip_zero = value != 0;
+    else if (!strcmp(name, "wave_env")) ctx->wave_env = value != 0;
+    else if (!strcmp(name, "wave_far_plan")) ctx->wave_far_plan = value != 0;
     else {
 #ifdef GSUM_LAB
         return gs_set_option_lab(ctx, name, value);

@@ -136,8 +136,8 @@ int gsum_kernel_profile(gsum_ctx* ctx, double* ms5, double* flops5, int64_t* lau
     }
     ctx->prof_recs.clear();
     ctx->prof_next = 0;
-    ctx->prof_tiles = 0;
-    if (ctx->prof_tiles_run) GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, sizeof(unsigned)));
+    ctx->prof_tiles = ctx->prof_panel_groups = 0;
+    if (ctx->prof_tiles_run) GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, GS_PROF_COUNTERS * sizeof(unsigned)));
     return 0;
 }
 

@@ -76,6 +76,9 @@ struct gs_wave_group {
     bool own_sc = false;                 // groups 0 and 1 borrow slot 0's panel and auxiliary streams (see gs_wave_prepare)
     hipEvent_t evChain = nullptr, evBulk = nullptr;
     gs_wv_pool pool;                     // `cap` workspaces at fixed strides
+    int* plan_list = nullptr;            // live-tile lists of the far updates (k_far_plan_g): plan_cap ids per workspace ...
+    unsigned* plan_count = nullptr;      // ... and their counts
+    int plan_cap = 0;
     int cap = 0;
     int64_t n = 0;                       // order the pool was allocated for
     // state inside a call
@@ -242,8 +245,17 @@ struct gsum_ctx {
                                      // tiles multiply only the span of operand panels in which their rows of A and of B are flagged (kernels/zwin.h):
                                      // on a banded kernel matrix (a short length scale on a long grid) nearly every tile returns at once.  0: null flag
                                      // pointers everywhere -- the dense launches.  Same G, sum log L_ii, info and factor (zeros may differ in sign)
-    unsigned* prof_tiles_run = nullptr;   // diagnostics (profile_gemm): far-update tiles of the batch schedule that multiplied, counted on the device ...
-    int64_t prof_tiles = 0;               // ... of this many launched (gsum_get_option "bulk_tiles_run" / "bulk_tiles"; gsum_kernel_profile resets both)
+    int wave_env = 1;                // the kernel build records, per 16-row group of a batch's matrices, the first 256-column panel in which it wrote anything
+                                     // but +-0 on or below the diagonal, and the panel solves' waves of groups that are still all zero return before they
+                                     // load a row (kernels/chain.hip.h, gs_wv_env_dead; with wave_skip_zero on only).  0: every wave loads.  Same bits everywhere
+    int wave_far_plan = 1;           // a small kernel lists the live tiles of every far update of a batch (those with a needed operand panel, by the
+                                     // panel solves' flags) and the far kernel's workgroups behind the count leave on one scalar load (kernels/tile.hip.h,
+                                     // k_far_plan_g; with wave_skip_zero on only).  0: every workgroup reads its own flags.  Same bits everywhere
+#define GS_PROF_COUNTERS 3
+    unsigned* prof_tiles_run = nullptr;   // diagnostics (profile_gemm), counted on the device: [0] far-update tiles of the batch schedule that multiplied ...
+    int64_t prof_tiles = 0;               // ... of this many launched (gsum_get_option "bulk_tiles_run" / "bulk_tiles"; gsum_kernel_profile resets both);
+    int64_t prof_panel_groups = 0;        // [1] panel-solve waves that loaded their rows, of this many launched ("panel_groups_loaded" / "panel_groups");
+                                          // [2] the sum of the far-update plans' live counts ("bulk_tiles_listed")
     int wave_tile128_rows = 0;       // far updates of at least this many rows on the 128 x 128 workgroup tile (k_gemm_ld3g2); 0 (default): never.  Alone the
                                      // tile is +2.7 % at M = 15120 and +1.5 % at 11280; inside a batch it LOSES (profiles/r05_tile128.log: n = 16384 45.4
                                      // against 45.6 evals/s, n = 12288 104.6 / 105.3, n = 8192 from 6144 rows 327.8 / 333.7): two 66-KB workgroups of

@@ -115,20 +115,23 @@ static int gs_check_desc(gsum_ctx* ctx, const gsum_kernel_desc* desc, int d) {
 
 // Kernel-matrix build launcher: picks the template instance (family, one-dimensional fast path) of k_build2.
 // tri != 0: lower 128-column tiles of a square padded matrix only.
+// env (the batch schedule only; null everywhere else): the workspace's row-group envelope, prow / 16 ints that the caller has set to
+// prow / 256 -- the build lowers them (gs_env_note).
 template <bool CROSS>
 static int gs_launch_build(gsum_ctx* ctx, hipStream_t s, double* out, int64_t ldo, const double* X, const double* Y, int64_t n,
-                           int64_t m, int64_t prow, int64_t pcol, int d, const gsum_kernel_desc* desc, double diag_add, int tri) {
+                           int64_t m, int64_t prow, int64_t pcol, int d, const gsum_kernel_desc* desc, double diag_add, int tri,
+                           int* env = nullptr) {
     const int64_t tr = (prow + GS_B2_ROWS - 1) / GS_B2_ROWS, tc = (pcol + 127) / 128, t128 = (prow + 127) / 128;
     const int64_t blocks = tri ? 4 * (t128 * (t128 + 1) / 2) : tr * tc;
     if (desc->n_ops > 0) {                      // a general Sum / Product tree: entry-by-entry evaluation (k_build_tree)
         hipLaunchKernelGGL((k_build_tree<CROSS>), dim3((unsigned)blocks), dim3(256), 0, s, out, ldo, X, Y, (int)n, (int)m, (int)prow,
-                           (int)pcol, d, *desc, diag_add, tri);
+                           (int)pcol, d, *desc, diag_add, tri, env);
         GS_CHECK(hipGetLastError());
         return 0;
     }
 #define GS_B2_LAUNCH(FAM, D1)                                                                                              \
     hipLaunchKernelGGL((k_build2<CROSS, FAM, D1>), dim3((unsigned)blocks), dim3(256), 0, s, out, ldo, X, Y, (int)n, (int)m, \
-                       (int)prow, (int)pcol, d, *desc, diag_add, tri)
+                       (int)prow, (int)pcol, d, *desc, diag_add, tri, env)
     const bool d1 = d == 1;
     switch (desc->family) {
         case GSUM_RBF: if (d1) GS_B2_LAUNCH(GSUM_RBF, true); else GS_B2_LAUNCH(GSUM_RBF, false); break;

@@ -17,9 +17,12 @@
 // (same kernels' bodies, same K = 256 / K = 512 pairing of the trailing updates): G, sum log L_ii and info are bit-identical to it.
 static void gs_wave_free_group(gs_wave_group* g) {
     for (void* q : {(void*)g->pool.A, (void*)g->pool.Ltab, (void*)g->pool.Lsib, (void*)g->pool.logdet, (void*)g->pool.diag0,
-                    (void*)g->pool.info, (void*)g->pool.res, (void*)g->pool.zfl})
+                    (void*)g->pool.info, (void*)g->pool.res, (void*)g->pool.zfl, (void*)g->pool.env, (void*)g->plan_list, (void*)g->plan_count})
         if (q) (void)hipFree(q);
     memset(&g->pool, 0, sizeof g->pool);
+    g->plan_list = nullptr;
+    g->plan_count = nullptr;
+    g->plan_cap = 0;
     g->cap = 0;
     g->n = 0;
 }
@@ -42,7 +45,8 @@ static void gs_wave_release(gsum_ctx* ctx, bool streams) {
 static double gs_wave_ws_bytes(int64_t np) {
     const double T = (double)(np / GS_NB);
     return (double)(np + GS_BORDER) * (double)GS_LD(np) * 8.0 + T * GS_LTAB * 8.0 + (T / 2 + 1) * GS_LSIB * 8.0 +
-           (T + (double)np + (double)GS_RES_LEN) * 8.0 + 4.0 + (double)(np / (2 * GS_NB)) * (double)((np + GS_BORDER) / 16);
+           (T + (double)np + (double)GS_RES_LEN) * 8.0 + 4.0 + (double)(np / (2 * GS_NB)) * (double)((np + GS_BORDER) / 16) +
+           (double)(np / 16) * 4.0 + (double)gs_tri_tiles64(np + GS_BORDER - 2 * GS_NB) * 4.0 + 4.0;
 }
 
 // G groups in all, the first Gs of them with a chain stream of their own; group i >= Gs (a second cohort) runs on group (i - Gs)'s
@@ -93,6 +97,12 @@ static int gs_wave_prepare(gsum_ctx* ctx, int G, int B, int64_t n, int64_t np, i
         if (e == hipSuccess) e = hipMalloc((void**)&p.res, (size_t)B * GS_RES_LEN * sizeof(double));
         // (never cleared: every flag a trailing update reads was written by a panel solve of the same round, see gs_panel256_body)
         if (e == hipSuccess) e = hipMalloc((void**)&p.zfl, (size_t)B * (size_t)(np / (2 * GS_NB)) * (size_t)((np + GS_BORDER) / 16));
+        // (set to np / 256 before every round's builds, which lower it: gs_lml_wave)
+        if (e == hipSuccess) e = hipMalloc((void**)&p.env, (size_t)B * (size_t)(np / 16) * sizeof(int));
+        // the live-tile lists of the far updates (k_far_plan_g): one per workspace, sized for the largest triangle (behind the first panel)
+        g->plan_cap = (int)gs_tri_tiles64(np + GS_BORDER - 2 * GS_NB);
+        if (e == hipSuccess) e = hipMalloc((void**)&g->plan_list, (size_t)B * (size_t)g->plan_cap * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->plan_count, (size_t)B * sizeof(unsigned));
         if (e != hipSuccess) {
             gs_wave_free_group(g);
             ctx->err = std::string("hipMalloc(group workspaces) failed: ") + hipGetErrorString(e);
@@ -129,10 +139,13 @@ static void gs_wave_bulk_plan(int64_t np, int depth, int64_t deep_min_rows, int 
     }
 }
 
-static int gs_wave_fill_chain(const gs_wave_group* g, gs_wv_chain_args* a, bool panel_counts, bool skip_zero = false) {
+static int gs_wave_fill_chain(const gs_wave_group* g, gs_wv_chain_args* a, bool panel_counts, bool skip_zero = false, bool env = false,
+                              unsigned* loaded = nullptr) {
     a->p = g->pool;
     a->n = g->cnt;
     a->zon = skip_zero ? 1 : 0;
+    a->eon = env ? 1 : 0;
+    a->pld = loaded;
     const int naug = g->pool.np + GS_BORDER;
     int run = 0;
     for (int e = 0; e < g->cnt; ++e) {
@@ -237,8 +250,8 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
     const bool prof = ctx->profile_gemm > 0;
     if (prof) ctx->prof_this_eval = true;
     if (prof && !ctx->prof_tiles_run) {
-        GS_CHECK(hipMalloc((void**)&ctx->prof_tiles_run, sizeof(unsigned)));
-        GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, sizeof(unsigned)));
+        GS_CHECK(hipMalloc((void**)&ctx->prof_tiles_run, GS_PROF_COUNTERS * sizeof(unsigned)));      // (GS_PROF_COUNTERS words: context.hip.h)
+        GS_CHECK(hipMemset(ctx->prof_tiles_run, 0, GS_PROF_COUNTERS * sizeof(unsigned)));
     }
     // everything of this call follows what the context's main stream has done so far (the resident inputs' upload)
     hipStream_t s0 = ctx->slots[0].sm;
@@ -259,10 +272,16 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 g->step = 0;
                 g->active = true;
                 ++live;
+                // the envelope of this round's matrices (option wave_env; with the zero flags only: wave_skip_zero = 0 stays the dense launches, whose
+                // panel waves solve their zero rows): every group "never written" (S), lowered by the builds below.  Off: the builds get a null
+                // pointer and the panel solves do not ask.
+                const bool env_on = ctx->wave_env != 0 && ctx->wave_skip_zero != 0;
+                if (env_on) GS_CHECK(hipMemsetD32Async((hipDeviceptr_t)g->pool.env, S, (size_t)g->cnt * (size_t)(np / 16), g->run));
                 for (int e = 0; e < g->cnt; ++e) {
                     const int rec = gs_prof_begin(ctx, g->run, GS_PROF_BUILD, 0.0);
                     const int rc = gs_launch_build<false>(ctx, g->run, g->pool.A + (int64_t)e * g->pool.strideA, ld, ctx->in->X, nullptr, n, n,
-                                                          np, np, d, &kernels[next + e], nugget, ctx->build_lower_only);
+                                                          np, np, d, &kernels[next + e], nugget, ctx->build_lower_only,
+                                                          env_on ? g->pool.env + (int64_t)e * (np / 16) : nullptr);
                     gs_prof_end(ctx, g->run, rec);
                     if (rc) return rc;
                 }
@@ -300,7 +319,9 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 }
                 {
                     hipStream_t spn = serial ? wv->sb : g->run;
-                    const int groups = gs_wave_fill_chain(g, &ca, true, ctx->wave_skip_zero != 0);
+                    const int groups = gs_wave_fill_chain(g, &ca, true, ctx->wave_skip_zero != 0, ctx->wave_env != 0 && ctx->wave_skip_zero != 0,
+                                                          prof ? ctx->prof_tiles_run + 1 : nullptr);
+                    if (prof) ctx->prof_panel_groups += groups;
                     const int rec = gs_prof_begin(ctx, spn, GS_PROF_PANEL, (double)g->cnt * 4.0 * (double)mrest * GS_NB * GS_NB);
                     if (ctx->wave_panel_wg4 == 8) hipLaunchKernelGGL(k_panel256gw<8>, dim3((unsigned)((groups + 7) / 8)), dim3(512), 0, spn, ca);
                     else if (ctx->wave_panel_wg4 && ctx->wave_panel_rows_lds) hipLaunchKernelGGL((k_panel256gw<4, true>), dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, spn, ca);
@@ -317,6 +338,32 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 const bool near = (st.near && ctx->wave_near_on_chain && !serial) || own_far;
                 last_on_chain = own_far;
                 hipStream_t su = near ? g->run : wv->sb;
+                // the far update's live tiles, listed on the chain stream behind the macro-step's last panel solve (option wave_far_plan; the 64-wide
+                // lower-triangle route with the flags on only -- near updates, the 128 x 128 tile, wave_serial and wave_skip_zero = 0 launch as before)
+                const bool planned = !st.near && !serial && ctx->wave_far_plan && ctx->wave_skip_zero &&
+                                     !(ctx->wave_tile128_rows > 0 && mrest >= ctx->wave_tile128_rows);
+                if (planned) {
+                    gs_wv_plan_args pa;
+                    pa.zfl = g->pool.zfl;
+                    pa.zstride = (int64_t)S * (naug / 16);
+                    pa.zps = (int)(naug / 16);
+                    pa.zg = (int)(r2 / 16);
+                    pa.first = st.first;
+                    pa.nP = st.K / (2 * GS_NB);
+                    pa.M = (int)mrest;
+                    pa.tiles = (int)gs_tri_tiles64(mrest);
+                    pa.pcap = g->plan_cap;
+                    pa.pad = 0;
+                    pa.pcount = g->plan_count;
+                    pa.plist = g->plan_list;
+                    pa.listed = (prof && !near) ? ctx->prof_tiles_run + 2 : nullptr;      // (counted where the launch's tiles are: ga.zrun below)
+                    for (int e = 0; e < g->cnt; ++e) pa.q[e] = (short)e;
+                    const size_t pshm = gs_plan_lds_counts(pa.nP, pa.M) + (GS_PLAN_THREADS / 64) * sizeof(unsigned);
+                    const int prec = gs_prof_begin(ctx, g->run, GS_PROF_OTHER, 0.0);
+                    hipLaunchKernelGGL(k_far_plan_g, dim3((unsigned)g->cnt), dim3(GS_PLAN_THREADS), pshm, g->run, pa);
+                    gs_prof_end(ctx, g->run, prec);
+                    GS_CHECK(hipGetLastError());
+                }
                 if (!near && !serial) {
                     GS_CHECK(hipEventRecord(g->evChain, g->run));
                     GS_CHECK(hipStreamWaitEvent(wv->sb, g->evChain, 0));
@@ -355,6 +402,10 @@ static int gs_lml_wave(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int n_ker
                 ga.zstride = (int64_t)S * (naug / 16);
                 ga.zps = (int)(naug / 16);
                 ga.zg = (int)(r2 / 16);
+                ga.pcount = planned ? g->plan_count : nullptr;
+                ga.plist = planned ? g->plan_list : nullptr;
+                ga.pcap = g->plan_cap;
+                ga.pad2 = 0;
                 // diagnostics (profile_gemm): tiles of the far updates that have something to subtract, counted on the device, beside the tiles
                 // launched (less the one tile past the last column that the plain grid of a small triangle carries)
                 ga.zrun = (prof && !near) ? ctx->prof_tiles_run : nullptr;

@@ -300,12 +300,21 @@ __device__ __forceinline__ void gs_b2_tile(int prow, int tri, int& bi, int& bj) 
     }
 }
 
+// The row-group envelope of the batch schedule (kernels/chain.hip.h, gs_wv_env_dead; env == null for every other caller: nothing
+// is read or written).  A wave of k_build2 / k_build_tree writes eight rows of ONE 16-row group `g`, 128 columns of ONE 256-column
+// panel `p`; `bits` is the OR of the value bits of its lane's entries on or below the diagonal of the rows that are stored.  Some
+// entry of the wave with bits other than +-0 (gs_panel16_any's rule: NaN and Inf count) lowers env[g] to p -- one atomic per wave,
+// and only for a wave that wrote something: most waves of a banded matrix write zeros and are done with the ballot.
+__device__ __forceinline__ void gs_env_note(int* env, unsigned long long bits, int g, int p, int lane) {
+    if (__ballot((bits << 1) != 0ull) != 0ull && lane == 0) atomicMin(env + g, p);
+}
+
 // One 32 x 128 tile per 256-thread workgroup: wave w takes rows 8 w .. 8 w + 7, two at a time; each lane owns two adjacent
 // columns (one 16-B store per row, 1 KiB per wave-instruction).  Grid: CROSS or tri == 0: (prow / 32 rounded up) x (pcol /
 // 128 rounded up) tiles, row-slice fastest; tri != 0: the 128-column tiles on or below the diagonal, four row slices each.
 template <bool CROSS, int FAM, bool D1>
 __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const double* X, const double* Y, int n, int m,
-                                                 int prow, int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri) {
+                                                 int prow, int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri, int* env) {
 #pragma clang fp contract(off)
     __shared__ double ui[GS_B2_ROWS * GSUM_MAX_D];
     __shared__ double uj[128 * GSUM_MAX_D];
@@ -349,6 +358,7 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
     const bool plain = CROSS ? (r0 + GS_B2_ROWS <= n && c0 + 128 <= m)
                              : (r0 + GS_B2_ROWS <= n && c0 + 128 <= n && (c0 + 128 <= r0 || r0 + GS_B2_ROWS <= c0));
     const double amp = desc.amplitude, addc = desc.additive_const;
+    unsigned long long ebits = 0ull;
 #pragma unroll 1
     for (int rp = 0; rp < 8; rp += 2) {
         double s[2][2], v[2][2];
@@ -372,9 +382,14 @@ __global__ __launch_bounds__(256) void k_build2(double* out, int64_t ldo, const 
             if (gi < prow) {
                 const gs_d2 o = {v[h][0], v[h][1]};
                 *reinterpret_cast<gs_d2*>(out + (int64_t)gi * ldo + gj0) = o;
+                if (!CROSS && env) {
+                    if (gj0 <= gi) ebits |= (unsigned long long)__double_as_longlong(v[h][0]);
+                    if (gj0 + 1 <= gi) ebits |= (unsigned long long)__double_as_longlong(v[h][1]);
+                }
             }
         }
     }
+    if (!CROSS && env && r0 + 8 * w < prow) gs_env_note(env, ebits, (r0 + 8 * w) >> 4, c0 >> 8, lane);
 }
 
 // ---- general kernel trees (gsum_kernel_desc with n_ops > 0) ----------------------------------------------------------------------
@@ -583,7 +598,7 @@ __device__ __forceinline__ void gs_build_tile128_tree(double* A, int64_t ld, con
 // kernel matrix of a tree: the tile geometry of k_build2 (32 x 128 tiles, a lane owns two adjacent columns), values through gs_tree_eval
 template <bool CROSS>
 __global__ __launch_bounds__(256) void k_build_tree(double* out, int64_t ldo, const double* X, const double* Y, int n, int m, int prow,
-                                                     int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri) {
+                                                     int pcol, int d, gsum_kernel_desc desc, double diag_add, int tri, int* env) {
 #pragma clang fp contract(off)
     const int t = threadIdx.x;
     int bi, bj;
@@ -598,6 +613,7 @@ __global__ __launch_bounds__(256) void k_build_tree(double* out, int64_t ldo, co
     for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int mm = 0; mm < GSUM_MAX_D; ++mm) xj[c][mm] = (mm < d && gj0 + c < ny) ? Yp[(int64_t)(gj0 + c) * d + mm] : 0.0;
+    unsigned long long ebits = 0ull;
     for (int rr = 0; rr < 8; ++rr) {
         const int gi = bi * GS_B2_ROWS + 8 * w + rr;
         if (gi >= prow) continue;
@@ -613,7 +629,12 @@ __global__ __launch_bounds__(256) void k_build_tree(double* out, int64_t ldo, co
         }
         const gs_d2 o = {v[0], v[1]};
         *reinterpret_cast<gs_d2*>(out + (int64_t)gi * ldo + gj0) = o;
+        if (!CROSS && env) {
+            if (gj0 <= gi) ebits |= (unsigned long long)__double_as_longlong(v[0]);
+            if (gj0 + 1 <= gi) ebits |= (unsigned long long)__double_as_longlong(v[1]);
+        }
     }
+    if (!CROSS && env && bi * GS_B2_ROWS + 8 * w < prow) gs_env_note(env, ebits, (bi * GS_B2_ROWS + 8 * w) >> 4, (bj * 128) >> 8, lane);
 }
 
 // Border rows np..np+15 of the augmented matrix: row c = column c of RHS (n x k, row-major), zero

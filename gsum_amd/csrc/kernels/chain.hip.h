@@ -273,15 +273,28 @@ struct gs_wv_pool {
     double* res;                             // one result record per workspace (k_finalize_g)
     int np, T;
     unsigned char* zfl;                      // zero flags of the solved panels, (np / 256) x ((np + 16) / 16) bytes per workspace (kernels/zwin.h)
+    int* env;                                // row-group envelope from the kernel build, np / 16 per workspace (option wave_env, gs_wv_env_dead)
 };
 // a panel launch's flag for 16-row group `group` below outer step `step` of workspace q; null with option wave_skip_zero off (a.zon)
 __device__ __forceinline__ unsigned char* gs_wv_zflag(const gs_wv_pool& p, bool on, int64_t q, int step, int64_t r2, int group) {
     const int64_t ps = (p.np + GS_BORDER) / 16;
     return on ? p.zfl + (q * (p.np / (2 * GS_NB)) + step) * ps + r2 / 16 + group : nullptr;
 }
+// The envelope: env[g] = the first outer step (256-column panel) in which the kernel build wrote, on or below the diagonal of 16-row group
+// g of the matrix rows, an entry with bits other than +-0 (gs_panel16_any's rule: NaN and Inf count); np / 256 when there is none.  A group
+// below outer step s with env[g] > s is all +-0 in every panel up to s as built, so -- by induction over the steps, zero rows solve to zero
+// and take nothing from the panels behind them -- it is all +-0 in panel s when that panel is solved: gs_panel256_body would load 16 x 256
+// zeros, store nothing and write flag 0.  The grouped entry kernels ask HERE, before any load; the border rows
+// (row >= np: the right-hand sides) always run.
+__device__ __forceinline__ bool gs_wv_env_dead(const gs_wv_pool& p, int64_t q, int step, int64_t row) {
+    const int g = __builtin_amdgcn_readfirstlane((int)(row >> 4));          // (a wave's rows are one group: a scalar load)
+    return g < p.np / 16 && p.env[q * (p.np / 16) + g] > step;
+}
 struct gs_wv_chain_args {
     gs_wv_pool p;
     int n, zon;                              // zon: the panel solves write (and use) the zero flags
+    int eon;                                 // the panel waves of dead row groups (gs_wv_env_dead) return before any load (option wave_env)
+    unsigned* pld;                           // diagnostics (profile_gemm): counts the panel waves that go on to load their rows; null otherwise
     short q[GS_WVC_MAX], step[GS_WVC_MAX];
     int end[GS_WVC_MAX];                     // k_panel256g: running counts of 16-row groups
 };
@@ -304,10 +317,15 @@ __global__ __launch_bounds__(64, 2) void k_panel256g(const gs_wv_chain_args a) {
     const int b = 2 * a.step[e];
     const int64_t c0 = (int64_t)b * GS_NB, r2 = c0 + 2 * GS_NB;
     const int M = a.p.np + GS_BORDER - (int)r2;
+    unsigned char* zflag = gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, bid - first);
+    if (a.eon && gs_wv_env_dead(a.p, q, a.step[e], r2 + 16 * (int64_t)(bid - first))) {
+        if (zflag && threadIdx.x == 0) *zflag = 0;
+        return;
+    }
+    if (a.pld && threadIdx.x == 0) atomicAdd(a.pld, 1u);
     gs_panel256_body(a.p.A + q * a.p.strideA + r2 * a.p.ld + c0, a.p.ld, M, a.p.Ltab + (q * a.p.T + b) * GS_LTAB,
                      a.p.Lsib + (q * (a.p.T / 2 + 1) + b / 2) * GS_LSIB, a.p.Ltab + (q * a.p.T + b + 1) * GS_LTAB,
-                     (unsigned long long*)nullptr, (unsigned long long*)nullptr, bid - first, (double*)nullptr,
-                     gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, bid - first));
+                     (unsigned long long*)nullptr, (unsigned long long*)nullptr, bid - first, (double*)nullptr, zflag);
 }
 // The same with W = 4 (or 8) waves per workgroup, each on its own 16-row group.  Single-wave workgroups are spread round-robin
 // over the CUs, and one 224-register panel wave on a SIMD is enough to keep a whole bulk workgroup (2 waves on EACH of the CU's 4
@@ -325,11 +343,16 @@ __global__ __launch_bounds__(64 * W, W == 4 ? 2 : 1) void k_panel256gw(const gs_
     const int b = 2 * a.step[e];
     const int64_t c0 = (int64_t)b * GS_NB, r2 = c0 + 2 * GS_NB;
     const int M = a.p.np + GS_BORDER - (int)r2;
+    unsigned char* zflag = gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, grp - first);
+    if (a.eon && gs_wv_env_dead(a.p, q, a.step[e], r2 + 16 * (int64_t)(grp - first))) {
+        if (zflag && (threadIdx.x & 63) == 0) *zflag = 0;
+        return;
+    }
+    if (a.pld && (threadIdx.x & 63) == 0) atomicAdd(a.pld, 1u);
     gs_panel256_body(a.p.A + q * a.p.strideA + r2 * a.p.ld + c0, a.p.ld, M, a.p.Ltab + (q * a.p.T + b) * GS_LTAB,
                      a.p.Lsib + (q * (a.p.T / 2 + 1) + b / 2) * GS_LSIB, a.p.Ltab + (q * a.p.T + b + 1) * GS_LTAB,
                      (unsigned long long*)nullptr, (unsigned long long*)nullptr, grp - first,
-                     TR ? tiles + (threadIdx.x >> 6) * GS_PT_TILE : (double*)nullptr,
-                     gs_wv_zflag(a.p, a.zon != 0, q, a.step[e], r2, grp - first));
+                     TR ? tiles + (threadIdx.x >> 6) * GS_PT_TILE : (double*)nullptr, zflag);
 }
 // entering evaluations: border rows <- RHS^T (k_set_border), grid ((np + 16) / 256 rounded up, entries)
 struct gs_wv_zsets { int64_t off[GS_WVC_MAX]; };         // per entry: offset (doubles) of its right-hand-side set in Z

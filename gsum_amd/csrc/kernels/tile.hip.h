@@ -24,13 +24,7 @@ __global__ __launch_bounds__(512) void k_mfma_peak(double* out, int iters) {
 // the bordered factorisation have 128 k + 16 rows (the right-hand-side rows), and with the partial tile row last, 2 tm + 2 tiles -- the longest
 // row of the triangle: 114 of 3306 at M = 7184 -- multiply for 16 valid rows each.  Rows [0, off) (off = M mod 128) form tile row 0 (c0 column
 // tiles), row bm >= 1 covers [off + 128 (bm - 1), off + 128 bm) and holds 2 bm + c0 column tiles: 3249 tiles at M = 7184.
-__host__ __device__ inline bool gs_tri_shifted(int M) { return (M & 127) != 0 && M > 128; }
-__host__ __device__ inline int64_t gs_tri_tiles64(int64_t M) {
-    const int64_t tm = (M + 127) / 128;
-    if (!gs_tri_shifted((int)M)) return tm * (tm + 1);
-    const int64_t off = M & 127, c0 = (off - 1) / 64 + 1, R = 1 + M / 128;
-    return c0 + (R - 1) * (R + c0);
-}
+// (gs_tri_shifted, gs_tri_tiles64 and the id -> tile maps of the grids without counted tiles: kernels/zwin.h, shared with the host)
 
 // ... with COUNTED tiles (the single-factorisation schedules: the tiles of the first 256 columns first, counted for the chain kernel; then,
 // in the deep schedule, column tiles 4 .. c2 - 1): how many tiles each group holds, for the host's wait counts and the kernel's id -> tile map.
@@ -191,19 +185,7 @@ __device__ __forceinline__ void gs_gemm_ld3_body(double* C, int64_t ldc, const d
         }
     } else if (tri == 1 && BNT == 1 && gs_tri_shifted(M)) {
         // the partial row tile first (gs_tri_tiles64): tile row 0 = rows [0, off), c0 column tiles; row bm >= 1 holds 2 bm + c0
-        const int off = M & 127, c0 = (off - 1) / 64 + 1;
-        const int bid = bid_in;
-        if (bid < c0) {
-            bm = 0;
-            bn = bid;
-        } else {
-            const int g = bid - c0;
-            bm = (int)((-(double)(c0 - 1) + sqrt((double)(c0 - 1) * (c0 - 1) + 4.0 * (double)(c0 + g))) * 0.5);
-            if (bm < 1) bm = 1;
-            while ((int64_t)(bm - 1) * (bm + c0) > g) --bm;
-            while ((int64_t)bm * (bm + 1 + c0) <= g) ++bm;
-            bn = g - (bm - 1) * (bm + c0);
-        }
+        gs_tile_tri_shift(M, bid_in, &bm, &bn);
         shifted = true;
     } else if (tri) {
         // lower tiles of a square C with 128 x 64 tiles: row bm holds column tiles 0 .. 2 bm + 1.
@@ -212,20 +194,15 @@ __device__ __forceinline__ void gs_gemm_ld3_body(double* C, int64_t ldc, const d
         // M = 8192 launch 813 -> 610 MB, its rate unchanged (55.0 vs 55.6 TF/s), the 16-in-flight pipeline 3 % SLOWER
         // (266.6 vs 274 evals/s: with sixteen queues dispatching at once workgroup ids no longer map to XCDs round-robin,
         // and the padding slots cost launches).  The kernel is not fetch-bound; the plain order stays.)
-        const int bid = bid_in;
-        bm = (int)((sqrt(4.0 * (double)bid + 1.0) - 1.0) * 0.5);
-        while ((int64_t)(bm + 1) * (bm + 2) <= bid) ++bm;
-        while ((int64_t)bm * (bm + 1) > bid) --bm;
-        bn = bid - (int)((int64_t)bm * (bm + 1));
+        gs_tile_tri_plain(bid_in, &bm, &bn);
     } else {
-        const int tm = (M + BM - 1) / BM;
-        bm = bid_in % tm;
-        bn = bid_in / tm;
+        gs_tile_rect(M, bid_in, &bm, &bn);
         first_cols = bid_in < nfirst;        // column-major tile order: the first 4 tm ids are the first 256 columns
     }
     // (shifted grid: tile row 0 ends at row off -- the rows behind it belong to tile row 1 -- and the full tile rows start there)
-    const int m0 = shifted ? (bm == 0 ? 0 : (M & 127) + (bm - 1) * BM) : bm * BM, n0 = bn * BN;
-    const int Mr = (shifted && bm == 0) ? (M & 127) : M;          // row bound of THIS tile
+    int m0, Mr;                                                   // Mr: row bound of THIS tile
+    gs_tile_rows(M, shifted, bm, &m0, &Mr);
+    const int n0 = bn * BN;
     if (n0 >= N) {                            // tri: the last row of a ragged matrix may have one column tile too many
         if (first_cols && t == 0) gs_flag_add(first_done);
         if (second_cols && t == 0) gs_flag_add(second_done);
@@ -544,20 +521,98 @@ struct gs_wv_gemm_args {
     const unsigned char* zfl; unsigned* zrun;
     int64_t zstride;
     int zps, zg;
+    // the live-tile lists of a far update (option wave_far_plan; k_far_plan_g below): workspace q's count and its list of pcap ids;
+    // null: every workgroup takes the tile of its own index -- the near updates, the 128 x 128 route, every launch with the option off
+    const unsigned* pcount; const int* plist;
+    int pcap, pad2;
 };
 __device__ __forceinline__ gs_zwin_view gs_wv_zview(const gs_wv_gemm_args& a, const gs_wv_gemm_entry& en) {
     return gs_zwin_view{a.zfl ? a.zfl + (int64_t)en.q * a.zstride : nullptr, a.zrun, en.first, a.zps, a.zg, a.zg};
 }
+// A far update's live tiles, listed before the launch (k_far_plan_g): workgroup i of an entry takes the i-th live tile of its member, in
+// ascending id order, and the workgroups behind the count leave on one scalar load (the same address for the whole entry) -- on a banded
+// matrix that is nearly all of a launch, which otherwise each load their flags, ballot and return.  GS_PLAN_ALL: every tile is live,
+// workgroup i takes tile i with no list load (a dense launch maps workgroups to tiles as it always did).
+#define GS_PLAN_ALL 0xffffffffu
 __device__ __forceinline__ void gs_gemm_ld3g_body(const gs_wv_gemm_args& a) {
     const int bid = (int)blockIdx.x;
     int e = 0;
     while (e + 1 < a.n && bid >= a.end[e]) ++e;
     const int first = e ? a.end[e - 1] : 0;
     const gs_wv_gemm_entry& en = a.e[e];
+    int tile = bid - first;
+    if (a.plist) {
+        const unsigned cnt = a.pcount[en.q];
+        if (cnt != GS_PLAN_ALL) {
+            if ((unsigned)tile >= cnt) return;
+            tile = a.plist[(int64_t)en.q * a.pcap + tile];
+        }
+    }
     double* W = a.base + (int64_t)en.q * a.strideA;
     const gs_zwin_view zv = gs_wv_zview(a, en);
     gs_gemm_ld3_body<2>(W + en.offC, a.ld, W + en.offA, a.ld, W + en.offB, a.ld, en.M, en.N, en.K, en.tri, 1, -1.0,
-                        (unsigned long long*)nullptr, 0, (unsigned*)nullptr, bid - first, 0, (unsigned*)nullptr, &zv);
+                        (unsigned long long*)nullptr, 0, (unsigned*)nullptr, tile, 0, (unsigned*)nullptr, &zv);
+}
+
+// The plan of one far update (lower triangle of M rows from row group zg on, operand panels [first, first + nP)): one workgroup of 1024
+// per member.  Wave p turns the member's flags of panel p, rows from zg on, into running counts in LDS (ballot + popcount, 64 groups a
+// step: nP x (M / 16 + 1) shorts, 4 x 450 at n = 8192); every tile id is decided by gs_zwin_tile_live_pre -- the body's own rule on those
+// counts -- 1024 ids per pass, and a ballot + prefix over the sixteen waves puts the live ids into the list in ascending order: the list
+// is the same on every run.  count = live tiles, or GS_PLAN_ALL when all `tiles` are live.
+// Runs on the chain stream behind the macro-step's last panel solve (whose flags it reads) and ahead of the event the far update waits for.
+#define GS_PLAN_THREADS 1024
+struct gs_wv_plan_args {
+    const unsigned char* zfl; int64_t zstride;       // as in gs_wv_gemm_args
+    int zps, zg, first, nP, M, tiles, pcap, pad;
+    unsigned* pcount; int* plist;
+    unsigned* listed;                                // diagnostics (profile_gemm): sum of the live counts; null otherwise
+    short q[GS_WV_MAX];
+};
+__host__ __device__ inline size_t gs_plan_lds_counts(int nP, int M) { return (((size_t)nP * (size_t)(M / 16 + 1) * sizeof(unsigned short)) + 3) & ~(size_t)3; }
+__global__ __launch_bounds__(GS_PLAN_THREADS) void k_far_plan_g(const gs_wv_plan_args a) {
+    constexpr int WAVES = GS_PLAN_THREADS / 64;
+    extern __shared__ unsigned short plan_pre[];     // [nP][ng + 1] running counts, then (4-byte aligned) the waves' live counts
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int64_t q = a.q[blockIdx.x];
+    const int ng = a.M / 16, stride = ng + 1;
+    unsigned* wsum = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(plan_pre) + gs_plan_lds_counts(a.nP, a.M));
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int p = w; p < a.nP; p += WAVES) {
+        const unsigned char* src = a.zfl + q * a.zstride + (int64_t)(a.first + p) * a.zps + a.zg;
+        unsigned run = 0;
+        for (int g0 = 0; g0 < ng; g0 += 64) {
+            const int g = g0 + lane;
+            const unsigned long long word = __ballot(g < ng && src[g] != 0);
+            if (g < ng) plan_pre[p * stride + g] = (unsigned short)(run + (unsigned)__popcll(word & below));
+            run += (unsigned)__popcll(word);
+        }
+        if (lane == 0) plan_pre[p * stride + ng] = (unsigned short)run;
+    }
+    __syncthreads();
+    int* list = a.plist + q * a.pcap;
+    unsigned total = 0;
+    for (int base = 0; base < a.tiles; base += GS_PLAN_THREADS) {
+        const int tile = base + t;
+        const bool live = tile < a.tiles && gs_zwin_tile_live_pre(a.M, tile, plan_pre, stride, a.nP);
+        const unsigned long long word = __ballot(live);
+        if (lane == 0) wsum[w] = (unsigned)__popcll(word);
+        __syncthreads();
+        unsigned before = total, all = 0;
+#pragma unroll
+        for (int v = 0; v < WAVES; ++v) {
+            const unsigned c = wsum[v];
+            before += v < w ? c : 0u;
+            all += c;
+        }
+        if (live) list[before + (unsigned)__popcll(word & below)] = tile;
+        total += all;
+        __syncthreads();
+    }
+    if (t == 0) {
+        a.pcount[q] = total == (unsigned)a.tiles ? GS_PLAN_ALL : total;
+        if (a.listed) atomicAdd(a.listed, total);
+    }
 }
 // k_gemm_ld3g: the big ("far") trailing updates, one after the other on the batch schedule's bulk stream.  k_gemm_ld3n: the same
 // code under a name of its own for the small "near" updates that run on the groups' chain streams BESIDE them -- so that a

@@ -101,6 +101,7 @@ const char* gsum_last_error(gsum_ctx* ctx);             /* NULL ctx: error of a 
  *                                  4 x groups x size evaluations runs two cohorts per group: twice as many in flight)
  *   "wave_skip_zero"  0 | 1        a batch's panel solves flag their 16-row groups that are not all +-0 and its trailing-update tiles skip
  *                                  the operand panels whose rows are all zero (a banded kernel matrix: nearly all); default 1, 0: dense launches
+ *   "wave_env", "wave_far_plan" 0 | 1   ... panel waves of row groups the build left all zero return before a load; far updates run listed live tiles
  *   "chain_persist"   -1 | 0 | 1   schedule of ONE factorisation: persistent chain kernel from order 768 up / never / whenever
  *                                  the order allows;  "lookahead" 0 | 1  look-ahead in the host-enqueued schedule
  *   "pivot_guard_ulps" 0..1024     a pivot p <= guard * eps * A_jj counts as not positive (default 2; process-wide)
@@ -270,7 +271,7 @@ int gsum_timers(gsum_ctx* ctx, double* ms, int32_t n);
 /* With "profile_gemm" on: summed HIP-event durations (ms), algorithmic flops and launch counts since the last call, five classes:
  * [0] kernel build, [1] diagonal blocks, [2] panel solves and near updates, [3] the bulk trailing update, [4] the rest; each launch
  * is timed on the stream it runs on (the bulk class of a batch runs on one stream: its sum is wall time).  Resets the record -- and
- * gsum_get_option "bulk_tiles" / "bulk_tiles_run": the far-update tiles the profiled batch calls launched / that had anything to subtract. */
+ * gsum_get_option "bulk_tiles" / "bulk_tiles_run" (far-update tiles launched / with anything to subtract), "panel_groups[_loaded]", "bulk_tiles_listed". */
 int gsum_kernel_profile(gsum_ctx* ctx, double* ms5, double* flops5, int64_t* launches5);
 #ifdef __cplusplus
 }
