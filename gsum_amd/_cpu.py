@@ -222,12 +222,19 @@ class CpuContext:
         return CpuMatrix(self, A)
 
     def potrf(self, M: CpuMatrix) -> int:
-        """numpy.linalg.cholesky's LAPACK call with its info (0 = success, k > 0: leading minor k is not positive definite)."""
+        """numpy.linalg.cholesky's LAPACK call with its info (0 = success, k > 0: leading minor k is not positive definite), under
+        netlib's pivot rule ``ajj <= 0 or isnan(ajj)``: an optimised LAPACK may leave out the NaN half and return info 0 with a NaN
+        factor.  Then the first NaN on the factor's diagonal is the pivot netlib refuses (every earlier diagonal entry is a finite
+        accepted pivot), and its 1-based index is info -- what the device returns."""
         self.calls["potrf"] += 1
         _refuse_failed(M, "potrf")
         if M.factored:
             raise ValueError("matrix is already factorised")
         c, info = dpotrf(M.A, lower=1, clean=1, overwrite_a=0)
+        if info == 0:
+            bad = np.flatnonzero(np.isnan(np.diagonal(c)))
+            if bad.size:
+                info = int(bad[0]) + 1
         if info == 0:
             M.A = c
             M.factored, M.pivoted = True, False

@@ -78,6 +78,15 @@ def _flatten(kernel):
     return terms, offset
 
 
+def _refuse_length_scale(ls, shown):
+    """A length scale of 0, below 0 or NaN is refused here, for every backend alike: the device library refuses such a descriptor
+    ("length_scale must be positive") where scikit-learn would build a matrix that is NaN off the diagonal.
+    +inf and huge values pass: they give the all-ones matrix."""
+    for v in ls:
+        if not v > 0.0:
+            raise ValueError(f"length_scale must be positive, got {float(v)!r} in {shown}")
+
+
 def _describe(terms, values, n_features, shown) -> KernelDesc:
     """``values(leaf)`` -> the leaf's hyperparameter; ``shown`` only feeds error messages."""
     if n_features < 1 or n_features > GSUM_MAX_D:
@@ -119,6 +128,7 @@ def _describe(terms, values, n_features, shown) -> KernelDesc:
         fam = "rbf"
     desc.family = FAMILY[fam]
     ls = np.atleast_1d(np.asarray(values(base), dtype=float))
+    _refuse_length_scale(ls, shown)
     if ls.size == 1:
         desc.anisotropic = 0
         desc.length_scale[0] = float(ls[0])
@@ -268,6 +278,8 @@ def _describe_tree(prog, theta, n_features, shown) -> KernelDesc:
             else:
                 lf.family = FAMILY["rbf"]
             ls = np.atleast_1d(np.asarray(ls, dtype=float))
+            if not isinstance(k, DotProduct):                                  # (sigma_0 = 0 is a valid DotProduct)
+                _refuse_length_scale(ls, shown)
             if ls.size == 1:
                 lf.anisotropic = 0
                 lf.length_scale[0] = float(ls[0])

@@ -132,13 +132,13 @@ int gsum_kernel_build_dev(gsum_ctx* ctx, const gsum_kernel_desc* desc, const dou
 /* A matrix handle is an INPUT (built or uploaded), a FACTOR (a factorisation reported *info == 0), a PIVOTED factor (of P^T A P, rows in
  * pivot order: gsum_sqrt_errors with pivot = 1) or FAILED (a factorisation reported *info > 0, or GSUM_ERR_CHAIN_ABORT).  "Refuses" below:
  * returns -2 with a message that names the call, and changes nothing.
- * upload a caller-built symmetric matrix (only its lower triangle is read) */
+ * upload a caller-built symmetric matrix (only its lower triangle is read: the strict upper one may hold anything, NaN included, and reaches no result) */
 int gsum_mat_from_host(gsum_ctx* ctx, const double* A, int64_t n, gsum_mat** out);
 /* numpy.linalg.cholesky(A), in place on the device.  Replaces models.py:711, 809, 969.  *info = LAPACK dpotrf's info.
  * GSUM_ERR_CHAIN_ABORT: the persistent-chain schedule of a single factorisation timed out (streams of the process did not run
  * side by side); the matrix is destroyed and the schedule switched off for the context -- rebuild the matrix and call again.
  * Refuses a FACTOR, a PIVOTED factor, a FAILED matrix.  *info > 0 leaves the matrix FAILED (it is partly overwritten): only
- * gsum_mat_to_host and gsum_mat_free take it from then on. */
+ * gsum_mat_to_host and gsum_mat_free take it from then on.  *info follows netlib dpotf2 on every schedule: the first pivot <= the guard OR NaN. */
 #define GSUM_ERR_CHAIN_ABORT (-3)
 int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info);
 /* W = L^-1 RHS (forward substitution only), G = W^T W (k x k), sum_log_diag = sum_i log L_ii.  Replaces the cho_solve calls
@@ -146,13 +146,13 @@ int gsum_potrf_lower(gsum_ctx* ctx, gsum_mat* A, int64_t* info);
  * Refuses an INPUT, a PIVOTED factor, a FAILED matrix, n != the order, k outside 1 .. GSUM_MAX_RHS.  The factor then HOLDS the solve. */
 int gsum_forward_gram(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, int32_t k, double* G, double* sum_log_diag);
 /* W = L^-1 RHS (n x k host): the forward half of cho_solve (models.py:479; with gsum_predict_terms: the solve at :831)
- * Refusals and the held solve as gsum_forward_gram. */
+ * Refusals and the held solve as gsum_forward_gram.  Operators on a factor: a non-finite entry stays in its column c (new point: its row q), all else bit-identical. */
 int gsum_forward_solve(gsum_ctx* ctx, gsum_mat* L, const double* RHS, int64_t n, int32_t k, double* W);
 /* X = cho_solve((L, True), B): both triangular solves of solve_sqrt (models.py:460-479); B, X n x k host, k <= GSUM_MAX_RHS
  * Refusals as gsum_forward_gram.  The factor holds NO solve afterwards (the back-substitution runs in place on the border rows). */
 int gsum_cho_solve(gsum_ctx* ctx, gsum_mat* L, const double* B, int64_t n, int32_t k, double* X);
 /* out = L Z (n x k): draws from N(mean, L L^T) without the n x n SVD of models.py:869-876, datasets.py:69-70
- * Refusals as gsum_forward_gram; a held solve stays. */
+ * Refusals as gsum_forward_gram; a held solve stays.  An entry in row r leaves rows < r of its column untouched (gsum_forward_solve, gsum_sqrt_errors: rows < 16 (r / 16)). */
 int gsum_tri_multiply(gsum_ctx* ctx, gsum_mat* L, const double* Z, int64_t n, int32_t k, double* out);
 /* Predictive pieces for m new points Xs (models.py:822-836) from the factor of kernel(X) + nugget: V = L^-1 kernel(X, Xs);
  * colsumsq[j] = sum_i V_ij^2;  VtW = V^T (L^-1 RHS) (m x k; NULL / k = 0 to skip);  cov_out (or NULL) = V^T V (m x m).
@@ -190,7 +190,7 @@ void gsum_mat_free(gsum_ctx* ctx, gsum_mat* A);
 /* ---- fused hot path: K build -> jittered Cholesky -> Gram / log-det, per kernel ---------------------------------------- */
 /* One full evaluation per descriptor, the work of one ConjugateGaussianProcess.log_marginal_likelihood call (models.py:958-1039):
  *   R = kernel_i(X) + nugget I;  L = chol(R);  W = L^-1 RHS;  G_i = W^T W;  sld_i = sum log diag L.
- * G_out n_kernels x k x k, sld_out n_kernels, info_out n_kernels (potrf info; G / sld undefined where > 0). */
+ * G_out n_kernels x k x k, sld_out n_kernels, info_out n_kernels (potrf info; G / sld undefined where > 0).  Non-finite inputs: one info on every route, members independent. */
 int gsum_lml_batch(gsum_ctx* ctx, const gsum_kernel_desc* kernels, int32_t n_kernels, const double* X, int64_t n, int32_t d,
                    const double* RHS, int32_t k, double nugget, double* G_out, double* sld_out, int64_t* info_out);
 /* The same with inputs resident in HBM: gsum_set_inputs uploads X and RHS once, gsum_lml_resident evaluates descriptors against
@@ -210,7 +210,7 @@ int gsum_lml_resident_sets(gsum_ctx* ctx, const gsum_kernel_desc* kernels, const
 /* Value AND gradient pieces of one evaluation (log_marginal_likelihood(theta, eval_gradient=True)).  Replaces
  * kernel(X, eval_gradient=True) (the n x n x p array at models.py:958, 1204), cho_solve(L, eye(N)) (:1044, 1266) and the einsum
  * contractions at :229, 276, 453-454, 1049.  With R = kernel(X) + nugget I, V = R^-1 RHS: G, sld, info as above;
- * trace_out[p] = tr(R^-1 dR_p);  H_out[p] (k x k) = V^T dR_p V.  dR_p is never materialised. */
+ * trace_out[p] = tr(R^-1 dR_p);  H_out[p] (k x k) = V^T dR_p V.  dR_p is never materialised.  Non-finite inputs: as gsum_lml_batch; info > 0: trace_out, H_out zeros. */
 int gsum_lml_grad(gsum_ctx* ctx, const gsum_kernel_desc* desc, const gsum_grad_param* params, int32_t n_params,
                   const double* X, int64_t n, int32_t d, const double* RHS, int32_t k, double nugget, double* G_out,
                   double* sld_out, int64_t* info_out, double* trace_out, double* H_out);
