@@ -6,7 +6,8 @@ Compute runs in libgsum_hip.so (hand-written HIP for gfx950, bound with ctypes);
 sort, percentile bands, interval coverage) in their own libgsum_refdist.so; the uncorrelated model ``TruncationPointwise`` (grid
 likelihood, credible-interval coverage) has its own libgsum_pointwise.so, the leave-one-out and leave-group-out diagnostics
 (``loo_from_factor``, ``kfold_from_factor``, ``Diagnostic.loo`` / ``.kfold``, ``ConjugateGaussianProcess.loo`` / ``.kfold``) their own libgsum_loo.so, the Toeplitz likelihood path for stationary kernels on uniform one-dimensional grids
-(``structure="toeplitz"``, ``toeplitz_column``, ``toeplitz_gram``, ``uniform_grid_step``) its own libgsum_toep.so, and ``hpd``, ``hpd_pdf``, ``median_pdf`` and ``cartesian`` are
+(``structure="toeplitz"``, ``toeplitz_column``, ``toeplitz_gram``, ``uniform_grid_step``) its own libgsum_toep.so, the banded likelihood path for short-range kernels on sorted one-dimensional points
+(``structure="banded"``, ``sorted_points``, ``banded_halfwidth``, ``banded_matrix``, ``banded_gram``, ``banded_forward``) its own libgsum_band.so, and ``hpd``, ``hpd_pdf``, ``median_pdf`` and ``cartesian`` are
 the reference's host helpers.  matplotlib is imported by ``GraphicalDiagnostic``'s plot
 methods when they are called, never by importing this package.  There is no CPU path except where a class takes ``backend='cpu'``.
 """
@@ -25,6 +26,7 @@ from .pointwise import TruncationPointwise
 from .loo import FoldResult, LooResult, kfold_from_factor, loo_from_factor, make_folds
 from .toeplitz import (toeplitz_column, toeplitz_grad, toeplitz_gradient_columns, toeplitz_gram, toeplitz_inverse_column, toeplitz_solve,
                        uniform_grid_step, toeplitz_predict, toeplitz_inverse_diagonal, toeplitz_loo, toeplitz_panel_width)
+from .banded import banded_forward, banded_gram, banded_halfwidth, banded_matrix, banded_max_halfwidth, sorted_points
 from .stats import hpd, hpd_pdf, median_pdf, cartesian
 from .grid import shard_range, gather_flat, lml_grid_distributed, predict_distributed
 from ._lib import HipContext, HipGroup, KernelDesc, default_context, default_group, device_count, lab_context, load_library
@@ -36,5 +38,6 @@ __all__ = [
     "make_gaussian_partial_sums_uniform", "make_gaussian_partial_sums_on_grid", "sample_mvn_cholesky", "shard_range", "gather_flat",
     "lml_grid_distributed", "Diagnostic", "pivoted_cholesky", "VariogramFourthRoot", "GraphicalDiagnostic", "refdist",
     "TruncationPointwise", "LooResult", "loo_from_factor", "FoldResult", "kfold_from_factor", "make_folds", "toeplitz_column", "toeplitz_gram", "uniform_grid_step", "toeplitz_inverse_column", "toeplitz_solve", "toeplitz_grad",
-    "toeplitz_gradient_columns", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo", "toeplitz_panel_width", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
+    "toeplitz_gradient_columns", "toeplitz_predict", "toeplitz_inverse_diagonal", "toeplitz_loo", "toeplitz_panel_width", "sorted_points", "banded_halfwidth", "banded_matrix",
+    "banded_gram", "banded_forward", "banded_max_halfwidth", "hpd", "hpd_pdf", "median_pdf", "cartesian", "predict_distributed", "HipContext", "HipGroup", "KernelDesc", "default_context", "default_group", "device_count", "lab_context", "load_library",
 ]

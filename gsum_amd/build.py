@@ -20,6 +20,9 @@
                         columns, and the gradient pieces from the first column of the inverse (Levinson's recursion,
                         Gohberg-Semencul), and the panel route that solves any number of columns from one recursion.  Its own
                         small library, built like the variogram's.
+``libgsum_band.so``     the banded likelihood path (include/gsum_band.h): kernel matrices in LAPACK band storage on sorted
+                        one-dimensional points, their batched band Cholesky, forward substitution and Gram matrices.  Its own small
+                        library, built like the variogram's; it includes kernels/build.hip.h for the kernel entries.
 The side libraries are the entries of ``SIDE``, built by ``build_side``; their host files share csrc/host/sidelib.hip.h.
 """
 from __future__ import annotations
@@ -46,7 +49,11 @@ SIDE_SCAFFOLD = os.path.join(HERE, "csrc", "host", "sidelib.hip.h")      # the h
 SIDE = {name: (os.path.join(HERE, "csrc", f"gsum_{name}.hip"), os.path.join(HERE, "csrc", f"gsum_{name}.map"),
                os.path.join(HERE, "csrc", "kernels", f"{kernels}.hip.h"), os.path.join(ROOT, "include", f"gsum_{name}.h"),
                os.path.join(HERE, f"libgsum_{name}.so"))
-        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"), ("loo", "loo"), ("toep", "toeplitz"))}
+        for name, kernels in (("vario", "variogram"), ("refdist", "refdist"), ("pointwise", "pointwise"), ("loo", "loo"), ("toep", "toeplitz"),
+                              ("band", "band"))}
+# what a side library includes beyond its own four files and the scaffold
+SIDE_EXTRA = {"band": [os.path.join(HERE, "csrc", "kernels", "build.hip.h"), os.path.join(HERE, "csrc", "kernels", "common.hip.h"),
+                       os.path.join(ROOT, "include", "gsum_hip.h")]}
 
 
 def hipcc_path():
@@ -63,7 +70,7 @@ def up_to_date(out=OUT, deps=None):
 def build_side(name: str, force: bool = False, verbose: bool = False) -> str:
     """libgsum_<name>.so: the product's hipcc flags, only gsum_<name>_* exported."""
     src, vmap, kernels, header, out = SIDE[name]
-    if not force and up_to_date(out, [src, vmap, kernels, header, SIDE_SCAFFOLD]):
+    if not force and up_to_date(out, [src, vmap, kernels, header, SIDE_SCAFFOLD] + SIDE_EXTRA.get(name, [])):
         return out
     cmd = [hipcc_path()] + HIPCC_FLAGS + ["-Wl,--version-script=" + vmap, "-o", out, src]
     if verbose:
@@ -90,6 +97,10 @@ def build_loo(force: bool = False, verbose: bool = False) -> str:
 
 def build_toep(force: bool = False, verbose: bool = False) -> str:
     return build_side("toep", force, verbose)
+
+
+def build_band(force: bool = False, verbose: bool = False) -> str:
+    return build_side("band", force, verbose)
 
 
 def build(force: bool = False, verbose: bool = False, lab: bool = False) -> str:

@@ -568,31 +568,47 @@ class ConjugateGaussianProcess:
     def _lml_structured(self, structure, thetas, eval_gradient, X, y, method="columns"):
         """The values of ``log_marginal_likelihood(theta, structure=...)`` for several theta (None: the fitted / given kernel): one
         first column per theta, one device call for all of them.  Everything the dense route would do silently differently is an error."""
-        if structure != "toeplitz":
-            raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+        if structure not in ("toeplitz", "banded"):
+            raise ValueError(f'structure must be None, "toeplitz" or "banded", got {structure!r}')
+        if eval_gradient and structure == "banded":
+            raise NotImplementedError('structure="banded" has no gradient: tr(A^-1 dA) needs the band of A^-1')
         if eval_gradient:
             raise NotImplementedError('structure="toeplitz" has no gradient: tr(T^-1 dT) needs the diagonal sums of T^-1')
-        from .toeplitz import toeplitz_gram
-        X, Z, cols, _ = self._structured_inputs(thetas, X, y)
-        G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend, method=method)
+        if structure == "banded":                                                    # DESIGN.md section 26
+            from .banded import gram_of_descs
+            X, Z, descs, _ = self._structured_inputs(thetas, X, y, structure)
+            G, sld, info = gram_of_descs(descs, X, self.nugget, Z, 1, device=self.device, backend=self.backend)
+        else:
+            from .toeplitz import toeplitz_gram
+            X, Z, cols, _ = self._structured_inputs(thetas, X, y)
+            G, sld, info = toeplitz_gram(cols, Z, 1, device=self.device, backend=self.backend, method=method)
         vals = self._lml_gram_batch(G[:, 0], sld, X.shape[0])
         return np.where(info != 0, -np.inf, vals)                                    # models.py:970-972
 
-    def _structured_inputs(self, thetas, X, y):
-        """(X, Z, the first column of every theta's kernel matrix, the kernel) of ``structure="toeplitz"``, after its checks."""
+    def _structured_inputs(self, thetas, X, y, structure="toeplitz"):
+        """(X, Z, the first column of every theta's kernel matrix, the kernel) of ``structure="toeplitz"``, after its checks;
+        ``structure="banded"``: every theta's descriptor in place of the column, X checked for one feature and order."""
         from .toeplitz import column_of_desc, uniform_grid_step
         self._check_decomposition()
         kernel = self._active_kernel()
         X = np.asarray(self.X_train_ if X is None else X, dtype=float)
         y = self.y_train_ if y is None else y
         if X.ndim != 2 or X.shape[1] != 1:
+            if structure == "banded":
+                raise ValueError(f'structure="banded" takes sorted one-dimensional points: X must have shape (n, 1), got {X.shape}')
             raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: X must have shape (n, 1), got {X.shape}')
-        uniform_grid_step(X)
+        if structure == "banded":
+            from .banded import sorted_points
+            sorted_points(X)
+        else:
+            uniform_grid_step(X)
         if self._many_curves(y):
-            raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
+            raise ValueError(f'structure="{structure}" takes at most {GSUM_MAX_RHS - 1} curves, got {np.shape(y)[1]}')
         Z = self._rhs(X, y)
         given = [t for t in thetas if t is not None]
         descs = iter(describe_thetas(kernel, given, 1)) if given else iter(())
+        if structure == "banded":
+            return X, Z, [next(descs) if t is not None else describe_kernel(kernel, 1) for t in thetas], kernel
         ctx = self._context()
         cols = np.stack([column_of_desc(ctx, next(descs) if t is not None else describe_kernel(kernel, 1), X, self.nugget) for t in thetas])
         return X, Z, cols, kernel
@@ -602,8 +618,10 @@ class ConjugateGaussianProcess:
         of its derivative by every hyperparameter, one device call for all of them (``toeplitz_grad``), then the host algebra of the
         dense route.  The values are those of the route without the gradient, bit for bit.  ``grad_method``: ``toeplitz_grad``'s
         ``method=`` (with ``"blocked"`` the values are those of ``toeplitz_method="blocked"``)."""
+        if structure == "banded":
+            raise NotImplementedError('structure="banded" has no gradient: tr(A^-1 dA) needs the band of A^-1')
         if structure != "toeplitz":
-            raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+            raise ValueError(f'structure must be None, "toeplitz" or "banded", got {structure!r}')
         from ._toep_lib import check_grad_method
         from .toeplitz import toeplitz_grad, toeplitz_gradient_columns
         check_grad_method(grad_method, "toeplitz_grad_method")
@@ -855,6 +873,8 @@ class ConjugateGaussianProcess:
         if not dense_factor and structure != "toeplitz":
             raise ValueError('dense_factor=False needs structure="toeplitz": there is no other route without the dense factor')
         if structure is not None:
+            if structure == "banded":
+                raise NotImplementedError('fit has no structure="banded": a calibration needs the gradient, which that route does not have')
             if structure != "toeplitz":
                 raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
             from .toeplitz import _is_stationary, uniform_grid_step
@@ -990,6 +1010,8 @@ class ConjugateGaussianProcess:
         """The route a call takes: its own ``structure=`` or, with None, the fit's ``structure_``."""
         if structure is None:
             return self.structure_ if self._fit else None
+        if structure == "banded":
+            raise NotImplementedError('predict and loo have no structure="banded": that route computes likelihood values only')
         if structure != "toeplitz":
             raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
         return structure

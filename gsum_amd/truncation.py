@@ -322,13 +322,16 @@ class TruncationGP:
         ``devices=`` / ``gather=``, more than 15 curves, a non-uniform X and a non-stationary kernel are errors, never a dense evaluation.
         ``toeplitz_method="panel"`` (``toeplitz_gram``'s ``method=``): all ratio settings ride one recursion per
         theta instead of one per few columns.
+        ``structure="banded"`` (``gsum_amd.banded``): the surface from the band of every theta's kernel matrix on
+        sorted one-dimensional points, uniform or not -- one band Cholesky per theta, every ratio setting a set of right-hand sides.
+        The same keywords and errors; a kernel whose half-bandwidth exceeds ``banded_max_halfwidth()`` is a ValueError.
         """
         if structure is not None:
-            if structure != "toeplitz":
-                raise ValueError(f'structure must be None or "toeplitz", got {structure!r}')
+            if structure not in ("toeplitz", "banded"):
+                raise ValueError(f'structure must be None, "toeplitz" or "banded", got {structure!r}')
             if devices is not None or gather != "host" or _ctx is not None:
-                raise ValueError('structure="toeplitz" runs on one device: devices= and gather= are not supported (shard= is)')
-            return self._grid_toeplitz(thetas, ratio_kws_list, scales, X, y, orders, mode, shard, toeplitz_method)
+                raise ValueError(f'structure="{structure}" runs on one device: devices= and gather= are not supported (shard= is)')
+            return self._grid_toeplitz(thetas, ratio_kws_list, scales, X, y, orders, mode, shard, toeplitz_method, structure)
         if devices is not None:
             if shard is not None:
                 raise ValueError("shard= (one process per GPU) and devices= (one process, several GPUs) exclude each other")
@@ -482,9 +485,11 @@ class TruncationGP:
         return shaped(out)
 
 
-    def _grid_toeplitz(self, thetas, ratio_kws_list, scales, X, y, orders, mode, shard, method="columns"):
+    def _grid_toeplitz(self, thetas, ratio_kws_list, scales, X, y, orders, mode, shard, method="columns", structure="toeplitz"):
         """The surface of ``structure="toeplitz"``: one first column per theta of this rank, one set [coefficients | 1] per ratio
-        setting, one device call; the prior scales only enter the host algebra."""
+        setting, one device call; the prior scales only enter the host algebra.  ``structure="banded"``: the band of every theta's
+        matrix in place of the first column (``banded.gram_of_descs``), everything else the same."""
+        from .banded import gram_of_descs, sorted_points
         from .grid import owned_points
         from .toeplitz import column_of_desc, toeplitz_gram, uniform_grid_step
         if mode not in ("full", "reuse"):
@@ -494,10 +499,13 @@ class TruncationGP:
         orders = self.orders_ if orders is None else orders
         Xd = np.asarray(X, dtype=float)
         if Xd.ndim != 2 or Xd.shape[1] != 1:
-            raise ValueError(f'structure="toeplitz" takes a one-dimensional grid: X must have shape (n, 1), got {Xd.shape}')
-        uniform_grid_step(Xd)
+            raise ValueError(f'structure="{structure}" takes a one-dimensional grid: X must have shape (n, 1), got {Xd.shape}')
+        if structure == "banded":
+            sorted_points(Xd)
+        else:
+            uniform_grid_step(Xd)
         if self._grid_many_curves(orders):
-            raise ValueError(f'structure="toeplitz" takes at most {GSUM_MAX_RHS - 1} curves')
+            raise ValueError(f'structure="{structure}" takes at most {GSUM_MAX_RHS - 1} curves')
         gp = self.coeffs_process
         ni, nj = len(ratio_kws_list), len(thetas)
         if scales is None:
@@ -514,10 +522,14 @@ class TruncationGP:
             js = np.unique((np.asarray(mine, dtype=np.int64) // ns) % nj)
             ctx = gp._context()
             descs = describe_thetas(gp._active_kernel(), [thetas[j] for j in js], 1)
-            cols = np.stack([column_of_desc(ctx, d, Xd, gp.nugget) for d in descs])
             Zs, dets = self._rhs_rows(Xd, y, orders, [kws if isinstance(kws, dict) else {"ratio": kws} for kws in ratio_kws_list])
             k = Zs.shape[2]
-            G, sld, info = toeplitz_gram(cols, Zs.transpose(1, 0, 2).reshape(n_pts, ni * k), ni, device=gp.device, backend=gp.backend, method=method)
+            Zall = Zs.transpose(1, 0, 2).reshape(n_pts, ni * k)
+            if structure == "banded":
+                G, sld, info = gram_of_descs(descs, Xd, gp.nugget, Zall, ni, device=gp.device, backend=gp.backend)
+            else:
+                cols = np.stack([column_of_desc(ctx, d, Xd, gp.nugget) for d in descs])
+                G, sld, info = toeplitz_gram(cols, Zall, ni, device=gp.device, backend=gp.backend, method=method)
             # (thetas, rows, scales) entries of the host algebra
             Gb = np.broadcast_to(G[:, :, None], (len(js), ni, ns, k, k)).reshape(-1, k, k)
             sb = np.broadcast_to(sld[:, None, None], (len(js), ni, ns)).reshape(-1)
